@@ -7,7 +7,12 @@ weight-gradient GEMM], (N>1: RCCL all-reduce of the gradients), Adam step (one f
 after the step, one host sync for the three logged losses. The step is one HIP-graph replay.
 Synthetic ballistic trajectories (bcnf_amd/data.py), device-resident, pre-shuffled; dropout active.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, last_loss, config).
+--full adds everything else the default workload measures, each in runs of its own after the timed steps: per-kernel
+HIP-event times and rooflines, log_prob errors against the reference's fixtures, the Trainer-shaped side figures, the
+CPU-oracle baseline and the `secondary` sub-lines (FC_large, LSTM_large, sampling, re-simulation).
+--dump-outputs DIR writes what the last timed step handed its caller (see dump_outputs) as DIR/<name>.npy.
 N>1: either launched by torch.distributed.run (RANK / WORLD_SIZE in the environment), or run directly, in which
 case this process -- before it touches the GPU -- starts `torch.distributed.run --nproc-per-node N` on itself as a
 child process and exits with the child's status. Prints ONE JSON line on rank 0.
@@ -126,6 +131,13 @@ def parse():
     ap.add_argument("--overlap-ranges", type=int, default=None,
                     help="wide workloads at world > 1: block ranges of the overlapped gradient all-reduce (default "
                          "4; 0 = one all-reduce after the backward, captured graphs)")
+    ap.add_argument("--full", action="store_true",
+                    help="fc_small: after the timed steps also measure the per-kernel times and rooflines, the log_prob "
+                         "errors against the reference's fixtures, the secondary figures and sub-lines and the CPU "
+                         "baseline (--no-secondary / --no-cpu-baseline take theirs out again). Off: the headline only. "
+                         "A run of one other --workload reports all of its own figures either way")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=12)
     ap.add_argument("--kernel-iters", type=int, default=20)
@@ -409,6 +421,60 @@ def spinup(fn, ms):
     return round((time.perf_counter() - t0) * 1e3, 1)
 
 
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all arrays of one run together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each (name, tensor / array) as path/<name>.npy, float64 for 64-bit floats and float32
+    for everything else. Arrays are written whole while the run's total stays within DUMP_BUDGET_BYTES; one that would
+    exceed its share of what is left is cut to a fixed sample of its flattened elements (sorted indices from
+    PCG64(0), the same for every run of the same shapes), written in place of the whole array under the same name."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES - 128 * len(arrays)        # the files count, .npy headers (128 bytes each) included
+    arrays = [(n, a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)) for n, a in arrays]
+    for i, (name, a) in enumerate(arrays):
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            keep = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def train_outputs(step, model, losses):
+    """What one training step hands its caller: the three logged values of the step (loss, nll, mse: the Trainer's
+    .item() reads), the parameters as the step's update left them (flattened in model.parameters() order) and the
+    gradients it left in .grad after the clip (of the tensors the step optimises, TrainStep.params: the coupling
+    stack's flat parameter buffer, then the feature network's)."""
+    out = [("losses", np.asarray(losses if losses is not None else [], dtype=np.float64)),
+           ("params", torch.cat([p.detach().reshape(-1) for p in model.parameters()]))]
+    grads = [p.grad.reshape(-1) for p in step.params if p.grad is not None]
+    if grads:
+        out.append(("grads", torch.cat(grads)))
+    return out
+
+
+class keep_dropout_stream:
+    """The dropout streams (the stack's device (seed, offset) with the host's feature-draw flag, and torch's own
+    generator of the device, which the LSTM feature network's dropout draws from) put back on exit as they were on
+    entry: the spin-up runs training-mode kernels for a wall-clock time, a different number of launches from run to
+    run, and the steps after it must draw the same masks every run (--dump-outputs compares builds output for output)."""
+
+    def __init__(self, fused):
+        self.fused = fused
+
+    def __enter__(self):
+        self.pending = self.fused._feature_pending
+        self.state = self.fused._rng_tensor().clone()
+        self.torch_state = torch.cuda.get_rng_state(self.state.device)
+
+    def __exit__(self, *exc):
+        self.fused._rng_tensor().copy_(self.state)
+        self.fused._feature_pending = self.pending
+        torch.cuda.set_rng_state(self.torch_state, self.state.device)
+
+
 def kernel_timing(model, data, args):
     """Average device time (us) of each launch of the NLL training pass on one batch, measured with HIP
     events on the launch stream around back-to-back launches (FusedStack.time_kernels)."""
@@ -486,7 +552,8 @@ def main():
         # device work without an idle gap
         step.prepare_epoch(max(args.steps, args.warmup))
     spin = argparse.Namespace(**{**vars(args), "kernel_iters": 4})
-    spun = spinup(lambda: kernel_timing(model, data, spin), args.spinup_ms)
+    with keep_dropout_stream(model.fused):
+        spun = spinup(lambda: kernel_timing(model, data, spin), args.spinup_ms)
     run_range(0, args.warmup)
     if not (args.indexed or args.per_step_sync):
         step.prepare_epoch(args.steps)      # (captured above: no capture lands in the timed region at any --warmup)
@@ -507,13 +574,11 @@ def main():
     value = world * args.batch * args.steps / dt
     seen = ranks_seen(world, device)
 
-    kern = kernel_timing(model, data, args) if rank == 0 else {}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(step, model, losses))
     line = None
     if rank == 0:
         B = args.batch
-        lp_abs, lp_rel = log_prob_error(model, device)
-        per_kernel = fc_small_rooflines(kern, B)
-        dom = max(per_kernel, key=lambda k: per_kernel[k]["avg_us"])   # the longest single launch, measured
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "samples/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "device_spinup_ms": spun, "ms_per_step": round(ms_per_step, 4),
@@ -524,18 +589,25 @@ def main():
             "config": {"workload": "trajectory_FC_small NLL training step (configs[1])", "batch_per_gpu": B,
                        "global_batch": B * world, "parallelism": f"dp{world}", "hip_graph": not args.no_graph,
                        "n_blocks": 32, "nested_sizes": [16] * 7, "n_conditions": 80, "dropout": 0.383},
+            "last_loss": losses[0] if losses else None,
+        }
+    if args.full and rank == 0:
+        kern = kernel_timing(model, data, args)
+        lp_abs, lp_rel = log_prob_error(model, device)
+        per_kernel = fc_small_rooflines(kern, B)
+        dom = max(per_kernel, key=lambda k: per_kernel[k]["avg_us"])   # the longest single launch, measured
+        line.update({
             "log_prob_max_abs_err": lp_abs, "log_prob_max_rel_err": lp_rel,
             "log_prob_err_other_fixtures": log_prob_errors_more(device),
-            "last_loss": losses[0] if losses else None,
             "roofline": dict(per_kernel[dom], kernel=dom),
             "roofline_kernels": per_kernel,
             "kernels_us": {k: round(v, 2) for k, v in kern.items()},
-        }
+        })
         if not args.no_secondary and world == 1 and not (args.indexed or args.per_step_sync):
             line["secondary"] = secondary_figures(step, args, device)
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(args)
-    if not args.no_secondary and not (args.indexed or args.per_step_sync):
+    if args.full and not args.no_secondary and not (args.indexed or args.per_step_sync):
         # configs[2], [3], [4] and re-simulation on every rank (the world's own scaling of each), each with its own
         # roofline and, at world 1, its own cpu_baseline (bounded)
         del step, model, data
@@ -550,7 +622,7 @@ def main():
         dist.destroy_process_group()
 
 
-# The sub-lines of the default run: (workload, timed steps). Per rank: FC_large 2048 / LSTM_large 1024 samples per step
+# The sub-lines of a --full run: (workload, timed steps). Per rank: FC_large 2048 / LSTM_large 1024 samples per step
 # (weak scaling; at world > 1 the backward's bucket slices are all-reduced while it runs, TrainStep overlap_ranges),
 # sampling's 1024 conditions and re-simulation's 1024 trajectories sharded over the ranks (strong scaling).
 SUBLINES = (("fc_large", 8), ("lstm_large", 8), ("sample", 30), ("resimulate", 5))
@@ -767,7 +839,7 @@ def wide_mfma_busy(workload):
 
 
 def run_wide(workload, batch, steps, warmup, world, rank, device, graph=True, kernel_iters=20, cpu=True,
-             cpu_batch=256, cpu_steps=4, overlap_ranges=0, spinup_ms=150.0):
+             cpu_batch=256, cpu_steps=4, overlap_ranges=0, spinup_ms=150.0, dump=None):
     """NLL-training samples/s of a wide workload (trajectory_FC_large = configs[2], trajectory_LSTM_large =
     configs[3]) per GPU, same step definition and timing contract as main(). Returns rank 0's JSON object."""
     from bcnf_amd import CondRealNVP_v2
@@ -792,7 +864,8 @@ def run_wide(workload, batch, steps, warmup, world, rank, device, graph=True, ke
     ka = _A()
     ka.kernel_iters = 2
     step.prepare_epoch(max(steps, warmup))      # captures first, then spin-up and warmup without an idle gap
-    spun = spinup(lambda: kernel_timing(model, data, ka), spinup_ms)
+    with keep_dropout_stream(model.fused):
+        spun = spinup(lambda: kernel_timing(model, data, ka), spinup_ms)
     step.run_epoch(warmup)
     step.prepare_epoch(steps)          # no graph capture inside the timed region
     if world > 1:
@@ -812,6 +885,8 @@ def run_wide(workload, batch, steps, warmup, world, rank, device, graph=True, ke
     seen = ranks_seen(world, device)
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, train_outputs(step, model, vals[-1] if vals else None))
     ka.kernel_iters = kernel_iters
     kern = kernel_timing(model, data, ka)
     B = batch
@@ -872,7 +947,7 @@ def main_wide(args):
     ov = args.overlap_ranges if args.overlap_ranges is not None else (OVERLAP_RANGES if world > 1 else 0)
     line = run_wide(args.workload, args.batch, args.steps, args.warmup, world, rank, device, graph=not args.no_graph,
                     kernel_iters=args.kernel_iters, cpu=not args.no_cpu_baseline, overlap_ranges=ov,
-                    spinup_ms=args.spinup_ms)
+                    spinup_ms=args.spinup_ms, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -880,7 +955,8 @@ def main_wide(args):
         dist.destroy_process_group()
 
 
-def run_sample(n_cond, steps, warmup, world, rank, device, n_draws=500, cpu=True, cpu_conds=1024, spinup_ms=150.0):
+def run_sample(n_cond, steps, warmup, world, rank, device, n_draws=500, cpu=True, cpu_conds=1024, spinup_ms=150.0,
+               dump=None):
     """Posterior draws/s (BASELINE configs[4]): 500 draws for each of `n_cond` conditions with trajectory_FC_small,
     the conditions sharded over the ranks (strong scaling of a fixed job; bcnf_amd/sampling.py), gathered at the end.
     One step = draw_sharded(500, all conditions) incl. feature net, device z draw, inverse, all-gather."""
@@ -896,7 +972,9 @@ def run_sample(n_cond, steps, warmup, world, rank, device, n_draws=500, cpu=True
     with model.fused.reuse_pack():
         # this rank's shard only (gather=False): the spin-up is time-bounded, so ranks run different counts of it,
         # and a collective inside would pair up across ranks wrongly
+        z_stream = gen.get_state()          # the spin-up's draw count varies from run to run; the steps' z must not
         spun = spinup(lambda: draw_sharded(model, n_draws, traj, generator=gen, gather=False), spinup_ms)
+        gen.set_state(z_stream)
         for _ in range(warmup):
             draw_sharded(model, n_draws, traj, generator=gen)
         if world > 1:
@@ -913,6 +991,8 @@ def run_sample(n_cond, steps, warmup, world, rank, device, n_draws=500, cpu=True
             tt = torch.tensor([dt], device=device)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if dump and rank == 0:
+            dump_outputs(dump, [("draws", out)])
         # dominant kernel: the inverse of this rank's n_draws x N_local rows, HIP events on the launch stream
         a, b = shard_range(n_cond, rank, world)
         with torch.no_grad():
@@ -1005,7 +1085,7 @@ def main_sample(args, n_draws=500):
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
     line = run_sample(args.batch, args.steps, args.warmup, world, rank, device, n_draws=n_draws,
-                      cpu=not args.no_cpu_baseline, spinup_ms=args.spinup_ms)
+                      cpu=not args.no_cpu_baseline, spinup_ms=args.spinup_ms, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -1044,7 +1124,8 @@ def resim_draws(n_traj, n_draws, seed=2024_03_25):
     return yh.astype(np.float32), data_dict
 
 
-def run_resim(n_traj, steps, warmup, world, rank, device, n_draws=1000, cpu=True, T=2.0, dt=1 / 15, spinup_ms=150.0):
+def run_resim(n_traj, steps, warmup, world, rank, device, n_draws=1000, cpu=True, T=2.0, dt=1 / 15, spinup_ms=150.0,
+              dump=None):
     """Re-simulated trajectories/s (resimulate with y_hat given, resimulation.py:21-59; notebooks/resimulation.ipynb
     sizes): n_draws x n_traj trajectories, the trajectories sharded over the ranks (independent, no collective).
     One step = bcnf_resimulate over this rank's draws, y_hat resident in HBM, (N, M, 30, 3) float64 written."""
@@ -1074,6 +1155,8 @@ def run_resim(n_traj, steps, warmup, world, rank, device, n_draws=1000, cpu=True
         tt = torch.tensor([el], device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    if dump and rank == 0:
+        dump_outputs(dump, [("positions", out)])
     # the kernel alone, HIP events on its launch stream; step attempts for the executed-work roofline. e0 is recorded
     # behind one launch already in the queue, so the host's per-call preparation (~60 us of Python + table upload)
     # overlaps a running kernel instead of leaving the GPU idle inside the window (round 3's 3-launch window started
@@ -1150,7 +1233,7 @@ def main_resim(args):
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
     line = run_resim(args.batch, args.steps, args.warmup, world, rank, device, cpu=not args.no_cpu_baseline,
-                     spinup_ms=args.spinup_ms)
+                     spinup_ms=args.spinup_ms, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:

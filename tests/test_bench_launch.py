@@ -36,6 +36,43 @@ def test_gpus2_launches_two_ranks():
         assert res["ranks_seen"] == 2 and res["n_gpus"] == 2, (wl, res)
 
 
+def test_dump_outputs_types_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 stays float64, everything else becomes float32; arrays within the budget are written
+    whole; one beyond its share is cut to a sample that is the same in every run and fills the share."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    rng = np.random.Generator(np.random.PCG64(5))
+    small = rng.standard_normal(3)                                   # float64, 24 bytes
+    half = torch.from_numpy(rng.standard_normal((7, 11))).to(torch.float16)
+    big = rng.standard_normal((50, 41)).astype(np.float32)          # 8200 bytes > what is left
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("small", small), ("half", half), ("big", big)])
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("small", "half", "big")}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in ("small", "half", "big")}
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["big.npy", "half.npy", "small.npy"]
+    assert a["small"].dtype == np.float64 and np.array_equal(a["small"], small)
+    assert a["half"].dtype == np.float32 and np.array_equal(a["half"], half.float().numpy())
+    assert a["big"].dtype == np.float32 and a["big"].ndim == 1
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 4096       # the files, headers included
+    assert a["big"].nbytes > 4096 - 3 * 128 - 24 - 7 * 11 * 4 - 4   # the sample uses what is left of the budget
+    flat = big.reshape(-1)
+    assert np.isin(a["big"], flat).all() and len(set(a["big"].tolist())) == a["big"].size
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 3 and args.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "somewhere"
+
+
 @pytest.mark.timeout(120)
 def test_gpus_disagreeing_with_world_size_fails():
     r = _run("--gpus", "2", "--launch-check", env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

@@ -8,9 +8,9 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-BENCH="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --kernel-iters 5"
+BENCH="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --kernel-iters 5"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- \
-  python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-secondary > $OUT/bench_under_trace.log 2>&1
+  python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-secondary > $OUT/bench_under_trace.log 2>&1
 echo trace_ok
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- $BENCH > $OUT/fetch.log 2>&1
 echo fetch_ok
