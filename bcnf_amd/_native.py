@@ -41,6 +41,7 @@ EXPORTS = (
     "bcnf_wide_fold_backward_range", "bcnf_wide_fold_backward_phase", "bcnf_wide_block_offset",
     "bcnf_wide_gemm_test", "bcnf_wide_backward_plan", "bcnf_rank_count", "bcnf_resimulate",
     "bcnf_guard_check_global", "bcnf_abi_version",
+    "bcnf_head_work_bytes", "bcnf_head_mse_forward", "bcnf_head_mse_backward", "bcnf_hybrid_finalize",
 )
 ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
 MAX_TENSORS = 48
@@ -197,6 +198,11 @@ def _bind(lib):
                                    ctypes.c_double, ctypes.c_double, _i32, _vp, _vp, _vp, _vp]),
         "bcnf_wide_gemm_test": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
         "bcnf_wide_backward_plan": (_i32, [_pdesc, _i64, _i32, _i32, _i32, _i32, _i32, _pi64]),
+        "bcnf_head_work_bytes": (_i32, [_i64, _i32, _i32, _pi64]),
+        "bcnf_head_mse_forward": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+        "bcnf_head_mse_backward": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, ctypes.c_float, _i64, _i32, _vp, _vp, _vp,
+                                          _i64, _i32, _vp]),
+        "bcnf_hybrid_finalize": (_i32, [_vp, _vp, _i64, _i32, ctypes.c_float, _vp, _vp]),
         "bcnf_status_string": (ctypes.c_char_p, [_i32]),
         "bcnf_abi_version": (_i32, []),
     }

@@ -28,7 +28,8 @@ from bcnf_amd.factories import FeatureNetworkFactory, LayerFactory
 from bcnf_amd.feature_network import (ConcatenateCondition, FeatureNetwork, FeatureNetworkStack,
                                       FullyConnectedFeatureNetwork, HIPLinear, LSTMFeatureNetwork, bind_rng_owner)
 from bcnf_amd.fft_stack import FFTWideStack
-from bcnf_amd.fused import FusedStack, StackConfig, stack_forward, stack_inverse, stack_nll, stack_nll_fold
+from bcnf_amd.fused import (FusedStack, StackConfig, stack_forward, stack_hybrid, stack_inverse, stack_nll,
+                            stack_nll_fold)
 from bcnf_amd.layers import AnyGLU, LinearFFTEnriched
 from bcnf_amd.wide import WideStack, make_stack, stack_nll_wide_fold
 from bcnf_amd.utils import ParameterIndexMapping, inn_nll_loss, log_prob_from_latent
@@ -539,6 +540,31 @@ class CondRealNVP_v2(ConditionalInvertibleLayer):
             raise ValueError("bcnf_amd: a deferred batch gather needs the folded feature path")
         condition = self._features(conditions)
         return stack_nll(self._fused, y, condition, self.training, defer=defer_reduction)
+
+    def hybrid_loss(self, y: torch.Tensor, *conditions: torch.Tensor, hybrid_weight: float,
+                    defer_reduction: bool = False) -> torch.Tensor:
+        """The Trainer's hybrid loss (trainer.py:261-269, hybrid_weight = w > 0): vals = [loss, nll, mse] with
+        mse = MSE(prediction_head(h), y) and loss = (nll + w * mse) / (1 + w), differentiable through ONE autograd
+        node on the fused NLL kernels of the stack's family plus the prediction-head kernels (bcnf_head_*). The head
+        reads h, so the feature network runs as in forward() and neither family's feature fold is taken. Under
+        no_grad the values are finalized (the validation triple of Trainer._validate_batch); defer_reduction as in
+        nll_loss. An AnyGLU (layerwise) stack computes the same three values with torch ops."""
+        if not self.hybrid:
+            raise ValueError("bcnf_amd: hybrid_loss needs a model built with hybrid=True (it has no prediction_head)")
+        w = float(hybrid_weight)
+        if not w >= 0.0:
+            raise ValueError(f"bcnf_amd: hybrid_weight must be >= 0, got {hybrid_weight}")
+        self._check_supported()
+        if y.dim() == 1:
+            y = y.unsqueeze(0)
+        h = self._features(conditions)
+        head = self.prediction_head
+        if self._path == "layerwise":
+            z, ldj = self._fused.forward(y, h)
+            nll = inn_nll_loss(z, ldj)
+            mse = torch.nn.functional.mse_loss(head(h), y)
+            return torch.stack([(nll + mse * w) / (1 + w), nll, mse])
+        return stack_hybrid(self._fused, y, h, head.weight, head.bias, w, self.training, defer=defer_reduction)
 
     # The training fast path for a feature stack that is ONE nn.Linear (ConcatenateCondition ->
     # FullyConnected(sizes=[X, C]), trajectory_FC_small): h = x Wf^T + bf only enters the stack through the

@@ -432,6 +432,15 @@ class FusedStack:
         N.check(rc, "bcnf_fold_nll_forward")
         return z, ldj, vals, (ws, pk)
 
+    # Hybrid loss (_HybridNLL). hybrid_cot = (cotangent of vals, [c0 / (1 + w), c1, 0], w): TrainStep's constant
+    # cotangent and its stack form, so the backward launches no kernel to derive one from the other. hybrid_judge:
+    # False in a data-parallel TrainStep, where the all-reduced loss is judged (bcnf_guard_check_global), not the shard's.
+    hybrid_cot = None
+    hybrid_judge = True
+
+    def hybrid_guard(self):
+        return self.guard if self.hybrid_judge else None
+
     # A BcnfFoldAdam for the next folded backward (TrainStep, multi-step graphs): consumed by that launch.
     pending_adam = None
     # (bucket, (flat offset, feature W offset, feature b offset)): TrainStep's data-parallel gradient bucket, which
@@ -651,6 +660,110 @@ def stack_nll(stack: FusedStack, y, h, training: bool, defer: bool = False):
     if torch.is_grad_enabled() and (params_grad or y.requires_grad or h.requires_grad):
         return _StackNLL.apply(y, h, fp if params_grad else fp.detach(), stack, training, defer)
     return stack.launch_nll_forward(y, h, training)[2]
+
+
+def head_workspace(B: int, K: int, D: int, device):
+    """Caller-owned workspace of the prediction-head kernels (bcnf_head_work_bytes): residual, MSE partials, split-K
+    partials of dW / dbias."""
+    nbytes = N.query_i64(N.lib().bcnf_head_work_bytes, ctypes.c_int64(B), ctypes.c_int32(K), ctypes.c_int32(D))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def launch_head_forward(h, wp, bp, y, work):
+    """r = h Wp^T + bp - y and the squared-error partials into `work` (bcnf_head_mse_forward)."""
+    B, K = h.shape
+    N.check(N.lib().bcnf_head_mse_forward(N.ptr(h), ctypes.c_int64(h.stride(0)), ctypes.c_int32(K), N.ptr(wp),
+                                          N.ptr(bp), N.ptr(y), ctypes.c_int64(B), ctypes.c_int32(y.shape[1]),
+                                          N.ptr(work), N.stream_handle(h.device)), "bcnf_head_mse_forward")
+
+
+def launch_head_backward(h, wp, work, dvals, weight: float, D: int, dwp, dbp, dh, accumulate: bool):
+    """dWp, dbp and dL/dh (added into `dh` with accumulate) of w / (1 + w) * mse (bcnf_head_mse_backward)."""
+    B, K = h.shape
+    N.check(N.lib().bcnf_head_mse_backward(N.ptr(h), ctypes.c_int64(h.stride(0)), ctypes.c_int32(K), N.ptr(wp),
+                                           N.ptr(work), N.ptr(dvals), ctypes.c_float(weight), ctypes.c_int64(B),
+                                           ctypes.c_int32(D), N.ptr(dwp), N.ptr(dbp), N.ptr(dh),
+                                           ctypes.c_int64(dh.stride(0) if dh is not None else K),
+                                           ctypes.c_int32(int(accumulate)), N.stream_handle(h.device)),
+            "bcnf_head_mse_backward")
+
+
+def launch_hybrid_finalize(vals, work, B: int, D: int, weight: float, guard):
+    """vals = [nll, nll, 0] -> [(nll + w mse) / (1 + w), nll, mse] (bcnf_hybrid_finalize)."""
+    N.check(N.lib().bcnf_hybrid_finalize(N.ptr(vals), N.ptr(work), ctypes.c_int64(B), ctypes.c_int32(D),
+                                         ctypes.c_float(weight), N.ptr(guard), N.stream_handle(vals.device)),
+            "bcnf_hybrid_finalize")
+
+
+class _HybridNLL(torch.autograd.Function):
+    """vals = [loss, nll, mse] of the Trainer's hybrid loss (trainer.py:261-269), loss = (nll + w mse) / (1 + w) with
+    mse = MSE(h Wp^T + bp, y), as ONE node: the fused NLL forward of the stack's family + the head forward; backward =
+    the stack's NLL backward with cotangent [dv0 / (1 + w), dv1, 0], the head backward adding its dL/dh into the
+    stack's, and (deferred reduction) the finalize of all three values."""
+
+    @staticmethod
+    def forward(ctx, y, h, flat_param, wp, bp, stack: FusedStack, training: bool, defer: bool, weight: float):
+        z, _, vals, saved = stack.launch_nll_forward(y, h, training, finalize=not defer)
+        B, D = y.shape
+        work = head_workspace(B, h.shape[1], D, y.device)
+        launch_head_forward(h, wp, bp, y, work)
+        if not defer:
+            launch_hybrid_finalize(vals, work, B, D, weight, stack.hybrid_guard())
+        ctx.stack, ctx.training, ctx.saved, ctx.defer, ctx.weight, ctx.work = stack, training, saved, defer, weight, work
+        ctx.has_bias = bp is not None
+        ctx.save_for_backward(h, z, vals, wp)
+        return vals
+
+    @staticmethod
+    def backward(ctx, dvals):
+        h, z, vals, wp = ctx.saved_tensors
+        stack, w, work = ctx.stack, ctx.weight, ctx.work
+        need_y, need_h, need_p, need_w, need_b = ctx.needs_input_grad[:5]
+        dvals = dvals.contiguous()
+        B, D = z.shape
+        hc = stack.hybrid_cot        # TrainStep: (its constant cotangent, that cotangent's stack form)
+        if hc is not None and hc[2] == w and dvals.data_ptr() == hc[0].data_ptr():
+            cot = hc[1]
+        else:
+            cot = dvals * dvals.new_tensor([1.0 / (1.0 + w), 1.0, 0.0])
+        dy, dh, dparams = stack.launch_nll_backward(h, z, cot, ctx.training, ctx.saved, want_dy=need_y,
+                                                    want_dh=need_h, finalize_into=vals if ctx.defer else None)
+        dwp = torch.empty_like(wp) if need_w else None
+        dbp = torch.empty(D, dtype=torch.float32, device=wp.device) if (need_b and ctx.has_bias) else None
+        if need_h or need_w or dbp is not None:
+            launch_head_backward(h, wp, work, dvals, w, D, dwp, dbp, dh, accumulate=True)
+        if need_y:       # d mse / dy = -e (rare: y is data); e = (2 g / (B D)) r, r = the workspace's first B * D floats
+            g = dvals[0] * (w / (1.0 + w)) + dvals[2]
+            dy = dy - (2.0 * g / (B * D)) * work[:B * D].view(B, D)
+        if ctx.defer:
+            launch_hybrid_finalize(vals, work, B, D, w, stack.hybrid_guard())
+        return dy, dh, (dparams if need_p else None), dwp, dbp, None, None, None, None
+
+
+def stack_hybrid(stack: FusedStack, y, h, wp, bp, weight: float, training: bool, defer: bool = False):
+    """[loss, nll, mse] of the hybrid loss on the fused stack + head kernels. h is materialised (the head reads it), so
+    neither family's feature fold applies. Without grad: finalized values (the Trainer's validation triple)."""
+    y = y.contiguous()
+    h = h.contiguous()
+    stack._check_device(y, h, wp, bp)
+    if tuple(wp.shape) != (y.shape[1], h.shape[1]) or not wp.is_contiguous() or \
+            (bp is not None and not bp.is_contiguous()):
+        raise ValueError(f"bcnf_amd hybrid loss: prediction head {tuple(wp.shape)} does not map features "
+                         f"{tuple(h.shape)} to {tuple(y.shape)}")
+    stack.sync_grad_state()
+    params_grad = stack.trainable[0].requires_grad
+    fp = stack.flat_param
+    any_grad = params_grad or y.requires_grad or h.requires_grad or wp.requires_grad or \
+        (bp is not None and bp.requires_grad)
+    if torch.is_grad_enabled() and any_grad:
+        return _HybridNLL.apply(y, h, fp if params_grad else fp.detach(), wp, bp, stack, training, defer,
+                                float(weight))
+    z, _, vals, _ = stack.launch_nll_forward(y, h, training)
+    B, D = y.shape
+    work = head_workspace(B, h.shape[1], D, y.device)
+    launch_head_forward(h, wp, bp, y, work)
+    launch_hybrid_finalize(vals, work, B, D, float(weight), stack.hybrid_guard())
+    return vals
 
 
 class _FoldNLL(torch.autograd.Function):

@@ -5,7 +5,7 @@
 
     optimizer.zero_grad()
     z, h = model(y, *conditions, log_det_J=True, return_features=True)
-    mse = MSE(prediction_head(h), y) if hybrid_weight > 0 else 0
+    mse = MSE(prediction_head(h), y) if hybrid_weight > 0 else 0     # configs/runs/hybrid/*: hybrid_weight 1
     nll = inn_nll_loss(z, model.log_det_J)
     loss = (nll + mse * w) / (1 + w)
     loss.backward()
@@ -15,10 +15,17 @@
     loss.item(), nll.item(), mse.item()
 
 MI355X specifics:
-* hybrid_weight == 0 (every shipped config): forward + loss are ONE fused launch (`model.nll_loss`,
+* hybrid_weight == 0 (configs/runs/old/*): forward + loss are ONE fused launch (`model.nll_loss`,
   bcnf_nll_forward) and loss.backward() is the fused NLL backward + deterministic slab reduce. A feature
   network that is one nn.Linear (trajectory_FC_small) is folded into the condition projection (no h, no
   dL/dh); other feature networks run on the library's MFMA GEMMs / PyTorch-ROCm.
+* hybrid_weight > 0 (configs/runs/hybrid/*, half of the reference's run configs): `model.hybrid_loss` -- one
+  autograd node: the same fused NLL kernels on the materialised h (no feature fold: the head reads h), the
+  prediction head + MSE as HIP kernels (bcnf_head_mse_forward / _backward, the head's dL/dh added into the
+  stack's in place) and bcnf_hybrid_finalize for the three logged values. Capture, run_epoch's multi-step
+  graphs and the device divergence guard (judging the combined loss) work as for hybrid_weight == 0; the folded
+  fused-Adam tail and the in-pack gather stay hybrid_weight == 0 only. `fuse_hybrid = False` keeps the generic
+  route (torch nn.Linear + MSELoss + autograd, one replay and one host sync per batch in run_epoch).
 * the coupling-stack parameters are ONE flat leaf (model.flat_parameters()); Adam is ONE launch over
   all parameters (bcnf_amd.optim.FusedAdam) that also emits the squared-gradient partials, so the
   clip after the step is one more launch.
@@ -70,6 +77,7 @@ class TrainStep:
         self.opt = FusedAdam(self.params, lr=lr)
         self.mse = torch.nn.MSELoss()
         self.fused_loss = self.hybrid_weight == 0.0
+        self._cot_stack = None
         self._cot = None
         self._graphs = None
         self._static = None
@@ -87,6 +95,7 @@ class TrainStep:
         self._gvals = None      # data parallel: the all-reduced (loss, nll, mse) -- a view of the bucket tail
         self._packed_inplace = False   # the last bucket pack found the gradients already in place
         self._host_cursor = 0   # host mirror of the epoch cursor (the history row of the next step)
+        self.last_clip_norm = None   # device scalar: total gradient norm before the last observable clip
         # data parallel, wide family: the backward runs in `overlap_ranges` block ranges and each finished range's
         # bucket slice is all-reduced (async) while the rest of the backward runs; eager steps (the collectives are
         # issued between kernel launches, outside any captured graph), joined before the update
@@ -152,6 +161,20 @@ class TrainStep:
             if adam is not None and self.model.fused.pending_adam is not None:
                 self.model.fused.pending_adam = None
                 raise RuntimeError("bcnf_amd TrainStep: the folded backward did not take the fused Adam update")
+            return vals.detach()
+        if self.hybrid:
+            vals = self.model.hybrid_loss(y, traj, hybrid_weight=self.hybrid_weight, defer_reduction=True)
+            if self._cot is None or self._cot.device != vals.device:
+                self._cot = torch.tensor([1.0, 0.0, 0.0], device=vals.device)
+                self._cot_stack = torch.tensor([1.0 / (1.0 + self.hybrid_weight), 0.0, 0.0], device=vals.device)
+            st = self.model.fused
+            st.hybrid_cot = (self._cot, self._cot_stack, self.hybrid_weight)
+            st.hybrid_judge = self.world == 1       # data parallel: the all-reduced loss is judged (_check_global)
+            try:
+                torch.autograd.backward(vals, self._cot)      # loss.backward()
+            finally:
+                st.hybrid_cot = None
+                st.hybrid_judge = True
             return vals.detach()
         z, h = self.model(y, traj, log_det_J=True, return_features=True)
         nll = inn_nll_loss(z, self.model.log_det_J)
@@ -335,7 +358,9 @@ class TrainStep:
             self.opt.clip_grad_norm_after_step(self.max_norm, cursor=cursor)
             return
         self.opt.step(defer_step_count=True, guard=self._guard)
-        self.opt.clip_grad_norm_after_step(self.max_norm, cursor=cursor, log=log, guard=self._guard)
+        # the pre-clip total norm (device scalar; the reference discards clip_grad_norm_'s return value)
+        self.last_clip_norm = self.opt.clip_grad_norm_after_step(self.max_norm, cursor=cursor, log=log,
+                                                                 guard=self._guard)
 
     def broadcast_parameters(self, src: int = 0):
         """Identical initial replicas (the RNG-seeded init differs per process otherwise)."""
@@ -631,7 +656,7 @@ class TrainStep:
             raise ValueError(f"run_epoch: {n} steps from batch {start} exceed the epoch's {nb} batches")
         if n == 0:
             return []
-        if not self.capture or not self.fused_loss:    # per-step host check (the device guard sits in
+        if not self.capture or self._no_fused_loss():  # per-step host check (the device guard sits in
             out = []                                     # the fused loss finalize), right after each update
             for i in range(n):                           # as trainer.py:166-168 does
                 v = self.step_epoch()
@@ -641,8 +666,11 @@ class TrainStep:
             return out
         self._ensure_epoch_graphs()
         self._guard.zero_()
-        if check_divergence:        # data parallel: judged on the all-reduced loss, the same on every rank
-            self._guard[GUARD_CHECK if self.world == 1 else GUARD_CHECK_GLOBAL] = 1
+        if check_divergence:
+            # data parallel: judged on the all-reduced loss, the same on every rank. Hybrid: the reference judges
+            # loss, not nll (trainer.py:168), so the stack's finalize must not judge nll alone -- the combined loss is
+            # judged by bcnf_hybrid_finalize (world 1) / bcnf_guard_check_global (world > 1)
+            self._guard[GUARD_CHECK if (self.world == 1 and not self.hybrid) else GUARD_CHECK_GLOBAL] = 1
         i = 0
         if self.world == 1 and self.epoch_unroll > 1:
             for k in self._unroll_sizes():
@@ -716,6 +744,19 @@ class TrainStep:
 
     # Hidden steps of a folded model update their parameters inside the backward tail (no Adam launch).
     fuse_adam = True
+    # hybrid_weight > 0 runs model.hybrid_loss (the head + MSE kernels, one autograd node). False: the generic route
+    # (torch nn.Linear + MSELoss, dz / dldj tensors, per-batch host sync in run_epoch) -- tests and A/B runs.
+    fuse_hybrid = True
+
+    @property
+    def hybrid(self) -> bool:
+        """hybrid_weight > 0 on a fused-stack model with fuse_hybrid on: the step runs model.hybrid_loss."""
+        return self.hybrid_weight > 0.0 and not self.layerwise and self.fuse_hybrid
+
+    def _no_fused_loss(self) -> bool:
+        """No fused loss finalize (hence no device guard, no multi-step graphs): an AnyGLU stack, or hybrid_weight > 0
+        with fuse_hybrid off."""
+        return self.layerwise or (self.hybrid_weight > 0.0 and not self.hybrid)
 
     def _fold_adam_slots(self):
         """(coupling flat parameter, feature weight, feature bias) when the fused-Adam tail applies: the model
@@ -751,7 +792,7 @@ class TrainStep:
     def prepare_epoch(self, n_steps: int):
         """Capture, without running anything, every graph a later run_epoch(n_steps) replays (the step graphs and,
         at world 1, the multi-step graph), so no capture lands inside a timed region."""
-        if self._epoch is None or not self.capture or not self.fused_loss:
+        if self._epoch is None or not self.capture or self._no_fused_loss():
             return
         self._ensure_epoch_graphs()
         if self.world == 1 and self.epoch_unroll > 1:

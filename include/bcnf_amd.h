@@ -429,6 +429,34 @@ int bcnf_wide_proj_rows(const BcnfStackDesc* desc, int64_t* rows);
 int bcnf_wide_inverse(const BcnfStackDesc* desc, const float* params, const void* packed, const float* z,
                       const float* h, int64_t h_rows, const int64_t* cond_index, int64_t n_rows, float* y,
                       int32_t training, const uint64_t* rng_state, void* scratch, void* stream);
+/* ---- Hybrid training loss: prediction head + MSE (cnf.py: prediction_head = nn.Linear(C, D); trainer.py:261-269
+ * with hybrid_weight w > 0: loss = (nll + w * MSE(prediction_head(h), y)) / (1 + w)) ---------------------------------
+ * x (B x K, rows ldx >= K floats apart; columns K .. ldx are never read into a result), W (D x K), bias (D, nullable),
+ * y (B x D); 2 <= D <= 32, K >= 1, B >= 1. fp32 MFMA (v_mfma_f32_16x16x4_f32). `work` is caller-owned, 16-byte
+ * aligned, bcnf_head_work_bytes(B, K, D) bytes: the residual r = x W^T + bias - y (its first B * D floats), the
+ * forward's squared-error partials and the split-K partials of dW / dbias. The three launching functions are
+ * stream-ordered, hold no state and reduce in a fixed order without float atomics: the same inputs give the same
+ * bits on every call and replay. `weight` is the host scalar w (>= 0).
+ *   forward:  r and per-workgroup sums of r^2 into `work`.
+ *   backward: e = (2 g / (B D)) r with g = dloss[0] w / (1 + w) + dloss[2], dloss the device cotangent of the three
+ *             logged values (NULL = [1, 0, 0]); dW (D x K) = e^T x and dbias (D) = column sums of e, split over the
+ *             batch and reduced by a second small launch; dx (B x K, rows ldd >= K apart) = e W, written, or with
+ *             accumulate_dx != 0 added into the existing dx (the stack's dL/dh: no separate add). Every output is
+ *             nullable.
+ *   finalize: after the stack's NLL finalize wrote loss_vals = [nll, nll, 0]: loss_vals[2] = mse = mean(r^2),
+ *             loss_vals[0] = (nll + w mse) / (1 + w); with guard[BCNF_GUARD_CHECK_GLOBAL] set the combined loss is
+ *             judged as bcnf_guard_check_global does (> 1e5 or NaN raises [BCNF_GUARD_DIVERGED]); a step already
+ *             [BCNF_GUARD_HALTED] is left alone. One workgroup. */
+int bcnf_head_work_bytes(int64_t batch, int32_t in_features, int32_t out_features, int64_t* bytes);
+int bcnf_head_mse_forward(const float* x, int64_t ldx, int32_t in_features, const float* weight_matrix,
+                          const float* bias, const float* y, int64_t batch, int32_t out_features, void* work,
+                          void* stream);
+int bcnf_head_mse_backward(const float* x, int64_t ldx, int32_t in_features, const float* weight_matrix, void* work,
+                           const float* dloss, float weight, int64_t batch, int32_t out_features, float* dweight,
+                           float* dbias, float* dx, int64_t ldd, int32_t accumulate_dx, void* stream);
+int bcnf_hybrid_finalize(float* loss_vals, const void* work, int64_t batch, int32_t out_features, float weight,
+                         int32_t* guard, void* stream);
+
 /* ---- Calibration (eval/calibration.py:20-48, compute_y_hat_ranks) -----------------------------------------------
  * counts[i * dim + d] += #{ s < n_draws : y_hat[(s * n_rows + i) * dim + d] < y[i * dim + d] } for the (n_draws, n_rows,
  * dim) draws of sample(outer=True); counts is uint32 and accumulates, so draws can be fed in chunks. */
