@@ -729,6 +729,37 @@ __device__ __forceinline__ void load_rows64(const float* __restrict__ M, long lo
   }
 }
 
+// load_rows64 in two steps, for a caller that wants every load of a round in flight before the first value is
+// used: load_rows64's ones-column select sits behind a branch per float4, which reads the loaded value before the
+// next load goes out (one round trip per float4). Same values as load_rows64.
+template <bool VEC>
+__device__ __forceinline__ void rows64_issue(const float* __restrict__ M, long long nrows, int ncols, long long ld,
+                                             long long r0, int c0, floatx4* reg) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int i4 = threadIdx.x + 256 * e, row = i4 >> 5, col = c0 + (i4 & 31) * 4;
+    const long long r = r0 + row < nrows ? r0 + row : nrows - 1;
+    if (VEC) {
+      reg[e] = *reinterpret_cast<const floatx4*>(M + r * ld + (col < ncols ? col : 0));
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) reg[e][q] = M[r * ld + (col + q < ncols ? col + q : ncols - 1)];
+    }
+  }
+}
+__device__ __forceinline__ void rows64_mask(long long nrows, int ncols, long long r0, int c0, floatx4* reg, int ones) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int i4 = threadIdx.x + 256 * e, row = i4 >> 5, col = c0 + (i4 & 31) * 4;
+    const bool in = r0 + row < nrows;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float v = (in && col + q < ncols) ? reg[e][q] : 0.f;
+      reg[e][q] = (in && col + q == ones) ? 1.f : v;
+    }
+  }
+}
+
 // HP tile: 64 rows x 64 columns kj. grid = (ceil(R/64), NKp/64)
 template <bool VEC>
 __global__ __launch_bounds__(BCNF_WG) void k_hp(BcnfLayout L, const float* __restrict__ pk,
@@ -872,17 +903,15 @@ __global__ __launch_bounds__(BCNF_WG) void k_dh(BcnfLayout L, const float* __res
 
 // dW1h split-K partials: 64 kj (4 blocks, one per wave) x all columns over one split of KC rows.
 // grid = (ceil(nb/4), splits); work[s][k][16][Cp]
-template <bool VEC, int BPW = 4>
+template <bool VEC>
 __device__ __forceinline__ void dw1h_body(const BcnfLayout& L, const float* __restrict__ d1, const float* __restrict__ h,
                                           long long B, int rows_per_split, float* __restrict__ work, int bx, int by,
-                                          float* __restrict__ smem, int ones = -1) {
+                                          float* __restrict__ smem) {
   const int hs = bstride16(L.Cp);
-  // BPW blocks per workgroup: 4 (one per wave, every column tile) or 2 (two waves per block, half the column
-  // tiles each: twice the workgroups, LDS for two resident per CU)
-  float* As = smem;                    // [16 BPW][KCP] (kj, b)
-  float* Bs = smem + 16 * BPW * KCP;   // [KC][hs]  (b, c)
+  float* As = smem;                    // [64][KCP] (kj, b)
+  float* Bs = smem + 64 * KCP;         // [KC][hs]  (b, c)
   const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, lr = l & 15, lq = l >> 4;
-  const int k0 = bx * BPW, s = by;
+  const int k0 = bx * 4, s = by;
   const long long m0 = (long long)s * rows_per_split;
   long long m1 = m0 + rows_per_split;
   if (m1 > B) m1 = B;
@@ -895,9 +924,9 @@ __device__ __forceinline__ void dw1h_body(const BcnfLayout& L, const float* __re
     const long long b = m0 + row;
     const bool ok = b < m1;
     const long long bb = ok ? b : m1 - 1;
-    floatx4 va[2 * BPW];
+    floatx4 va[8];
 #pragma unroll
-    for (int kk = 0; kk < BPW; ++kk) {
+    for (int kk = 0; kk < 4; ++kk) {
       const int k = k0 + kk < L.nb ? k0 + kk : L.nb - 1;
       const floatx4* src = reinterpret_cast<const floatx4*>(d1 + ((long long)k * B + bb) * 16 + j8);
       va[2 * kk] = src[0];
@@ -905,9 +934,9 @@ __device__ __forceinline__ void dw1h_body(const BcnfLayout& L, const float* __re
     }
     floatx4 rv[2][8];
 #pragma unroll
-    for (int half = 0; half < 2; ++half) load_rows64<VEC>(h, m1, L.C, L.ldh, m0 + 64 * half, 0, rv[half], ones);
+    for (int half = 0; half < 2; ++half) load_rows64<VEC>(h, m1, L.C, L.ldh, m0 + 64 * half, 0, rv[half]);
 #pragma unroll
-    for (int kk = 0; kk < BPW; ++kk) {
+    for (int kk = 0; kk < 4; ++kk) {
       const float m = (ok && k0 + kk < L.nb) ? 1.f : 0.f;
       const floatx4 v0 = va[2 * kk] * m, v1 = va[2 * kk + 1] * m;
 #pragma unroll
@@ -927,7 +956,7 @@ __device__ __forceinline__ void dw1h_body(const BcnfLayout& L, const float* __re
     for (int c0 = KC; c0 < L.Cp; c0 += KC) {           // Cp > 128 only
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
-        load_rows64<VEC>(h, m1, L.C, L.ldh, m0 + 64 * half, c0, rv[half], ones);
+        load_rows64<VEC>(h, m1, L.C, L.ldh, m0 + 64 * half, c0, rv[half]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const int i4 = tid + 256 * e, r = 64 * half + (i4 >> 5), col = c0 + (i4 & 31) * 4;
@@ -937,18 +966,15 @@ __device__ __forceinline__ void dw1h_body(const BcnfLayout& L, const float* __re
     }
   }
   __syncthreads();
-  const int kw = BPW == 4 ? wave : wave >> 1;
-  const int k = k0 + kw;
-  const int nh = BPW == 4 ? NC16 : (NC16 + 1) >> 1;
-  const int n_lo = BPW == 4 ? 0 : (wave & 1) * nh, n_hi = min(NC16, n_lo + nh);
+  const int k = k0 + wave;
   float* o = work + (((long long)s * L.nb + (k < L.nb ? k : 0)) * 16) * L.Cp;
-  for (int n = n_lo; n < n_hi; ++n) {
+  for (int n = 0; n < NC16; ++n) {
     floatx4 acc = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     for (int t0 = 0; t0 < KC / 4; t0 += 8) {            // LDS reads of 8 steps, then 8 MFMAs (2 chains)
       float a[8], bv[8];
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
-        a[t] = As[(16 * kw + lr) * KCP + 4 * (t0 + t) + lq];
+        a[t] = As[(16 * wave + lr) * KCP + 4 * (t0 + t) + lq];
         bv[t] = Bs[(4 * (t0 + t) + lq) * hs + 16 * n + lr];
       }
 #pragma unroll
@@ -975,22 +1001,113 @@ __global__ __launch_bounds__(BCNF_WG) void k_dw1h(BcnfLayout L, const float* __r
 
 size_t hp_lds_bytes() { return sizeof(float) * (size_t)(64 * KCP + KC * BNS); }
 size_t dh_lds_bytes() { return sizeof(float) * (size_t)(64 * KCP + KC * 16); }
-size_t dw1h_lds_bytes(const BcnfLayout& L, int bpw = 4) {
-  return sizeof(float) * (size_t)(16 * bpw * KCP + KC * bstride16(L.Cp));
-}
+size_t dw1h_lds_bytes(const BcnfLayout& L) { return sizeof(float) * (size_t)(64 * KCP + KC * bstride16(L.Cp)); }
 
-// Folded path, first launch of the backward tail: the split-K D1^T [x | 1] alone, two blocks per workgroup.
-template <bool VEC>
-__global__ __launch_bounds__(BCNF_WG) void k_fold_splitk(BcnfLayout F, const float* __restrict__ d1,
-                                                         const float* __restrict__ x, long long B, int rows_per_split,
-                                                         float* __restrict__ work, int gx_dw, int ones,
-                                                         FoldAdamArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  if (A.on && blockIdx.x == gridDim.x - 1) {       // one extra workgroup: the Adam scalars for k_red_gx / finish
-    if (threadIdx.x == 0) adam_scalars_publish(A);
-    return;
+// Folded path's split-K D1^T [x | 1]: the same partials as dw1h_body (work[s][k][16][Cp], one split of KC rows
+// each), shaped to share a launch with the slab reduce (k_fold_tail), whose workgroups all get this role's LDS:
+//   * two blocks per workgroup, two waves per block with half the column tiles each (twice the workgroups);
+//   * the split's KC rows staged as two KH-row halves, so a workgroup holds 4 (32 KHP + KH hs) B of LDS (37 KB at
+//     Xp = 96, four workgroups per CU; dw1h_body's whole-split staging of two blocks took 74 KB, two per CU);
+//   * each wave keeps acc / acc1 of its NT column tiles across the halves: per tile, t still runs 0 .. KC/4 - 1
+//     in order, alternating acc / acc1, then acc += acc1 -- dw1h_body's sums, bit for bit.
+// Every global load of a half is issued before its first LDS store: one memory round trip per half (both halves'
+// 80 staging registers held at once, or the second half's held under the first half's products, put the launch
+// below four waves per SIMD); the column chunks beyond KC of Cp > KC take a round trip of their own.
+constexpr int KH = KC / 2, KHP = KH + 4;
+template <bool VEC, int NT>
+__device__ __forceinline__ void dw1h_half_body(const BcnfLayout& L, const float* __restrict__ d1,
+                                               const float* __restrict__ h, long long B, int rows_per_split,
+                                               float* __restrict__ work, int bx, int by, float* __restrict__ smem,
+                                               int ones) {
+  const int hs = bstride16(L.Cp);
+  float* As = smem;                    // [32][KHP] (kj, b)
+  float* Bs = smem + 32 * KHP;         // [KH][hs]  (b, c)
+  const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, lr = l & 15, lq = l >> 4;
+  const int k0 = bx * 2, s = by;
+  const long long m0 = (long long)s * rows_per_split;
+  long long m1 = m0 + rows_per_split;
+  if (m1 > B) m1 = B;
+  const int NC16 = L.Cp >> 4;
+  // A: the 2 blocks' D1 rows [KH][16] of the half, one float4 per (thread, block); B: the half's rows of h
+  const int row = tid >> 2, j4 = (tid & 3) * 4;
+  floatx4 va[2], rv[8];
+  float am[2];
+  auto load_half = [&](int half) {
+    rows64_issue<VEC>(h, m1, L.C, L.ldh, m0 + KH * half, 0, rv);
+    const long long b = m0 + KH * half + row;
+    const bool ok = b < m1;
+    const long long bb = ok ? b : m1 - 1;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const int k = k0 + kk < L.nb ? k0 + kk : L.nb - 1;
+      va[kk] = *reinterpret_cast<const floatx4*>(d1 + ((long long)k * B + bb) * 16 + j4);
+      am[kk] = (ok && k0 + kk < L.nb) ? 1.f : 0.f;
+    }
+  };
+  const int kw = wave >> 1, k = k0 + kw;
+  const int nh = (NC16 + 1) >> 1, n_lo = (wave & 1) * nh, n_hi = min(NC16, n_lo + nh);   // nh <= NT
+  floatx4 acc[NT], acc1[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j] = acc1[j] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    load_half(half);
+    if (half) __syncthreads();                          // every wave is done with the first half's tiles
+    rows64_mask(m1, L.C, m0 + KH * half, 0, rv, ones);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int i4 = tid + 256 * e, r = i4 >> 5, col = (i4 & 31) * 4;
+      if (col < L.Cp) *reinterpret_cast<floatx4*>(Bs + r * hs + col) = rv[e];
+    }
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const floatx4 v = va[kk] * am[kk];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) As[(kk * 16 + j4 + q) * KHP + row] = v[q];
+    }
+    for (int c0 = KC; c0 < L.Cp; c0 += KC) {           // Cp > 128 only
+      rows64_issue<VEC>(h, m1, L.C, L.ldh, m0 + KH * half, c0, rv);
+      rows64_mask(m1, L.C, m0 + KH * half, c0, rv, ones);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int i4 = tid + 256 * e, r = i4 >> 5, col = c0 + (i4 & 31) * 4;
+        if (col < L.Cp) *reinterpret_cast<floatx4*>(Bs + r * hs + col) = rv[e];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int n = n_lo + j;
+      if (n >= n_hi) continue;
+#pragma unroll
+      for (int t0 = 0; t0 < KH / 4; t0 += 8) {          // LDS reads of 8 steps, then 8 MFMAs (2 chains)
+        float a[8], bv[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          a[t] = As[(16 * kw + lr) * KHP + 4 * (t0 + t) + lq];
+          bv[t] = Bs[(4 * (t0 + t) + lq) * hs + 16 * n + lr];
+        }
+#pragma unroll
+        for (int t = 0; t < 8; t += 2) {
+          acc[j] = mfma4(a[t], bv[t], acc[j]);
+          acc1[j] = mfma4(a[t + 1], bv[t + 1], acc1[j]);
+        }
+      }
+    }
   }
-  dw1h_body<VEC, 2>(F, d1, x, B, rows_per_split, work, blockIdx.x % gx_dw, blockIdx.x / gx_dw, smem, ones);
+  if (k >= L.nb) return;
+  float* o = work + (((long long)s * L.nb + k) * 16) * L.Cp;
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int n = n_lo + j;
+    if (n >= n_hi) continue;
+    const floatx4 r = acc[j] + acc1[j];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[(long long)(4 * lq + i) * L.Cp + 16 * n + lr] = r[i];
+  }
+}
+size_t dw1h_half_lds_bytes(const BcnfLayout& L) {
+  return sizeof(float) * (size_t)(32 * KHP + KH * bstride16(L.Cp));
 }
 
 __global__ __launch_bounds__(BCNF_WG) void k_dw1h_reduce(BcnfLayout L, const float* __restrict__ work, int splits,
@@ -1032,6 +1149,12 @@ __device__ __forceinline__ void gx_reduce_body(long long total, const float* __r
   gx[i] = acc;
 }
 
+// Folded path, second launch of the backward tail: the Gx sum alone (6 MB of partials at B = 4096).
+__global__ __launch_bounds__(BCNF_WG) void k_fold_gx(long long total, const float* __restrict__ work, int splits,
+                                                     float* __restrict__ gx) {
+  gx_reduce_body(total, work, splits, gx, (long long)blockIdx.x * BCNF_WG + threadIdx.x);
+}
+
 // Folded path, last launch of the backward: two small GEMMs as 16 x 16 output tiles, each operand K-chunk staged
 // in LDS as [k][16] in one memory round trip (every load of a chunk issued together: the operands were written by
 // other XCDs, so each access is an L2 miss and a streaming K loop of dependent round trips is what costs).
@@ -1040,6 +1163,8 @@ __device__ __forceinline__ void gx_reduce_body(long long total, const float* __r
 // Tile product: thread (ks = lane & 15, rb = lane >> 4, cb = wave) accumulates the 4 x 4 block rows 4rb.., cols
 // 4cb.. over k = ks + 16 i (conflict-free ds_read_b128: 16 consecutive rows x 4 float4 per wave), then the 16
 // k-slices are summed in a fixed order through LDS.
+// wf / bf are k_fold_tail's copy of the feature Linear in the tail's scratch, not the parameters: role b's fused
+// Adam updates those in place in this launch, and nothing orders role a's reads before it.
 __device__ __forceinline__ int c0_of_finish(int bx, int nct) { return (bx % nct) * 16; }
 
 constexpr int FIN_KC = 512;                           // K chunk: role a (Xp <= 256) and role b at nb <= 32
@@ -1090,12 +1215,12 @@ __global__ __launch_bounds__(BCNF_WG) void k_fold_finish(BcnfLayout L, const flo
   // fused Adam (FoldAdamArgs): this thread's output is one parameter whose gradient it computes; its parameter and
   // moments are fetched now, the update follows the tile product. The launch's last workgroup does the step's
   // bookkeeping (bcnf_adam_step_bookkeep semantics), workgroup 0 stores the logged values.
-  // The scalars come from k_fold_splitk (adam_scalars_publish); workgroup 0's log row index is loaded now and its
+  // The scalars come from k_fold_tail (adam_scalars_publish); workgroup 0's log row index is loaded now and its
   // system-scope stores issued once the operands are staged, their fence at the end (no round trip up front).
   const bool adam = A.on && !(A.guard && A.guard[BCNF_GUARD_HALTED]);
   AdamScalars as{};
   // Workgroup 0's thread 0 keeps the step's books (bcnf_adam_step_bookkeep semantics): it alone reads the step count
-  // and the cursor in this launch (the scalars came from k_fold_splitk), so it advances both itself at its end --
+  // and the cursor in this launch (the scalars came from k_fold_tail), so it advances both itself at its end --
   // no arrival counter, no last-workgroup round trip.
   const bool keeper = adam && blockIdx.x == 0 && tid == 0;
   const bool logger = keeper && A.log_values && A.log_history;
@@ -2459,7 +2584,7 @@ __device__ __forceinline__ float sum_rows4(float v) {
 //            (Linear 1: only its y-part columns; the condition part is the split-K GEMM of the tail)
 //   sum job c: 16 column sums at SUM_OFF + 16 c (lanes 0..15)
 // The slab layout is decoded by slab_to_canonical. The MFMA tiles are written through (sc1), like the forward's
-// records: k_red_gx reads them from memory anyway.
+// records: k_fold_tail reads them from memory anyway.
 template <int NH>
 __device__ __forceinline__ void bwd_grad_jobs(const float* __restrict__ Td, const float* __restrict__ Ta,
                                               float* __restrict__ out, int hw) {
@@ -2780,11 +2905,18 @@ __device__ __forceinline__ long long slab_to_canonical(const BcnfLayout& L, int 
 constexpr int RED_G = 8, RED_O4 = 32, RED_T = 16;
 
 // With `A` (folded training step inside a multi-step graph, FoldAdamArgs): the reduced gradient of each output also
-// takes its Adam update here; the parameters / moments are fetched before the slab stream, the scalars are `as`.
+// takes its Adam update here; the parameters / moments are fetched before the slab stream. The step's two scalars
+// are derived in the workgroup (adam_scalars' arithmetic on threads 0 and 64: no earlier launch to publish them to
+// this one) once the first round of slab loads is out, and reach the updating threads through LDS and the barrier
+// the reduction has anyway: no round trip and no barrier of their own (r06: 5.9 us with the two pows in front of the
+// first load).
+constexpr int RED_SMEM = RED_G * RED_O4 * 4 + 4;      // floats: the partial sums, then the two scalars
+
 __device__ __forceinline__ void reduce_body(const BcnfLayout& L, const float* __restrict__ slab, long long stride,
                                             int nwg, float* __restrict__ out, int bx, float* __restrict__ smem,
-                                            const FoldAdamArgs* A = nullptr, const AdamScalars* as = nullptr) {
+                                            const FoldAdamArgs* A = nullptr) {
   floatx4 (*part)[RED_O4] = reinterpret_cast<floatx4 (*)[RED_O4]>(smem);   // [RED_G][RED_O4]
+  float* sc = smem + RED_G * RED_O4 * 4;
   const int g = threadIdx.x / RED_O4, o4 = threadIdx.x % RED_O4;
   const long long i = ((long long)bx * RED_O4 + o4) * 4;
   const bool live = i < stride;
@@ -2792,6 +2924,7 @@ __device__ __forceinline__ void reduce_body(const BcnfLayout& L, const float* __
   const int m = (int)(ic / L.sblk), o = (int)(ic - (long long)m * L.sblk);
   long long ci[4];
   float ap[4], am[4], av[4];
+  const float step0 = A ? A->step[0] : 0.f;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     ci[e] = slab_to_canonical(L, m, o + e);
@@ -2802,6 +2935,13 @@ __device__ __forceinline__ void reduce_body(const BcnfLayout& L, const float* __
       av[e] = A->v[0][c];
     }
   }
+  bool scalars_due = A != nullptr;
+  auto scalars = [&]() {
+    const double t = (double)(step0 + 1.0f);
+    if (threadIdx.x == 0) sc[0] = (float)(A->lr / (1.0 - pow(A->b1, t)));
+    if (threadIdx.x == 64) sc[1] = (float)sqrt(1.0 - pow(A->b2, t));
+    scalars_due = false;
+  };
   floatx4 acc = {0.f, 0.f, 0.f, 0.f};
   int w = g;
   for (; w + RED_G * (RED_T - 1) < nwg; w += RED_G * RED_T) {
@@ -2809,22 +2949,26 @@ __device__ __forceinline__ void reduce_body(const BcnfLayout& L, const float* __
 #pragma unroll
     for (int t = 0; t < RED_T; ++t)
       v[t] = *reinterpret_cast<const floatx4*>(slab + (long long)(w + RED_G * t) * stride + ic);
+    if (scalars_due) scalars();                        // under the loads just issued
 #pragma unroll
     for (int t = 0; t < RED_T; ++t) acc += v[t];
   }
   for (; w < nwg; w += RED_G) acc += *reinterpret_cast<const floatx4*>(slab + (long long)w * stride + ic);
+  if (scalars_due) scalars();                          // fewer than RED_G RED_T slabs: no full round above
   part[g][o4] = acc;
   __syncthreads();
   if (g != 0 || !live) return;
   floatx4 tot = part[0][o4];
 #pragma unroll
   for (int q = 1; q < RED_G; ++q) tot += part[q][o4];
+  AdamScalars as{};
+  if (A) as = adam_scalars_of(*A, sc[0], sc[1]);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     if (ci[e] < 0) continue;
     out[ci[e]] = tot[e];
     if (A) {
-      adam_elem(ap[e], tot[e], am[e], av[e], *as);
+      adam_elem(ap[e], tot[e], am[e], av[e], as);
       A->p[0][ci[e]] = ap[e];
       A->m[0][ci[e]] = am[e];
       A->v[0][ci[e]] = av[e];
@@ -2839,12 +2983,10 @@ struct TailGrid {
   int n_dh, gx_dh;      // dh tiles: (gx_dh x Cp/16), 0 if dh is not requested
   int n_red;            // slab-reduce workgroups
   int gx_dw;            // dW1h: (gx_dw x splits)
-  int ones;             // folded path: the split-K runs on x1 = [x | 1] (ones column index), else -1
 };
 
-// Lw: the split-K role's layout (L itself, or fold_layout(L, X) with h = x on the folded path).
 template <bool VEC>
-__global__ __launch_bounds__(BCNF_WG) void k_bwd_tail(BcnfLayout L, BcnfLayout Lw, TailGrid G, const float* __restrict__ pk,
+__global__ __launch_bounds__(BCNF_WG) void k_bwd_tail(BcnfLayout L, TailGrid G, const float* __restrict__ pk,
                                                       const float* __restrict__ d1, const float* __restrict__ h,
                                                       long long B, float* __restrict__ dh,
                                                       const float* __restrict__ slab, long long stride, int nwg,
@@ -2862,28 +3004,59 @@ __global__ __launch_bounds__(BCNF_WG) void k_bwd_tail(BcnfLayout L, BcnfLayout L
     return;
   }
   i -= G.n_red;
-  dw1h_body<VEC>(Lw, d1, h, B, rows_per_split, work, i % G.gx_dw, i / G.gx_dw, smem, G.ones);
+  dw1h_body<VEC>(L, d1, h, B, rows_per_split, work, i % G.gx_dw, i / G.gx_dw, smem);
 }
 
-// Folded path, second launch of the backward tail: the Gx reduce (latency-bound, 6 MB) placed first, then the
-// slab reduce (HBM-bound, 75 MB at B = 4096), so the former hides under the latter; the split-K that produces
-// the Gx partials ran alone in the launch before (the two roles in one launch did not overlap: 28 us vs 13 + 10).
-__global__ __launch_bounds__(BCNF_WG) void k_red_gx(BcnfLayout L, long long total, const float* __restrict__ work,
-                                                    int splits, float* __restrict__ gx, int n_gx,
-                                                    const float* __restrict__ slab, long long stride, int nwg,
-                                                    float* __restrict__ dparams, FoldAdamArgs A) {
-  __shared__ __attribute__((aligned(16))) float smem[RED_G * RED_O4 * 4];
+// Folded path, first launch of the backward tail: the split-K D1^T [x | 1] (latency-bound: 27 MB and 0.4 GFLOP at
+// B = 4096, waiting on D1 rows k_backward wrote from other XCDs) and the slab reduce (HBM-bound, 90 MB) depend on
+// k_backward alone and share this launch. Block-index ranges, in dispatch order:
+//   [0, n_sk)   split-K workgroups (dw1h_half_body), first, so their round trip starts at once and the stream of the
+//               reduce fills the machine behind them;
+//   n_sk        one workgroup: copies [Wf | bf] into the tail's scratch for k_fold_finish (which Adam-updates the
+//               tensors themselves) and publishes the step's Adam scalars for it;
+//   the rest    slab reduce (reduce_body), with the fused Adam's scalars derived in each workgroup.
+// The order is for speed only: no role reads what another role of this launch writes.
+// An earlier one-launch tail (r01j) measured 28 us against 13 + 10 for two launches, for two reasons that were not
+// the overlap itself: its grid put the split-K last, so the latency-bound role ran alone at the end, and every
+// workgroup carried the split-K's 74 KB of LDS, so the ~625 reduce workgroups (2.4 per CU, which must all be
+// resident to keep their loads in flight) ran two per CU in two rounds. Here the split-K leads and stages 37 KB.
+template <bool VEC, int NT>
+__global__ __launch_bounds__(BCNF_WG, VEC && NT <= 3 ? 4 : 2) void k_fold_tail(BcnfLayout L, BcnfLayout F, const float* __restrict__ d1,
+                                                       const float* __restrict__ x, long long B, int rows_per_split,
+                                                       float* __restrict__ work, int gx_dw, int n_sk, int ones,
+                                                       const float* __restrict__ slab, long long stride, int nwg,
+                                                       float* __restrict__ dparams, const float* __restrict__ wf,
+                                                       const float* __restrict__ bf, float* __restrict__ wf1,
+                                                       FoldAdamArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
   const int bx = blockIdx.x;
-  if (bx < n_gx) {
-    gx_reduce_body(total, work, splits, gx, (long long)bx * BCNF_WG + threadIdx.x);
+  if (bx < n_sk) {
+    dw1h_half_body<VEC, NT>(F, d1, x, B, rows_per_split, work, bx % gx_dw, bx / gx_dw, smem, ones);
+    return;
+  }
+  if (bx == n_sk) {
+    const int nw = L.C * F.C, n1 = nw + (bf ? L.C : 0);   // wf1 = Wf [C][X], then bf [C]
+    for (int i0 = 0; i0 < n1; i0 += 16 * BCNF_WG) {
+      float v[16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = min(i0 + e * BCNF_WG + (int)threadIdx.x, n1 - 1);
+        v[e] = i < nw ? wf[i] : bf[i - nw];
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = i0 + e * BCNF_WG + (int)threadIdx.x;
+        if (i < n1) wf1[i] = v[e];
+      }
+    }
+    if (A.on && threadIdx.x == 0) adam_scalars_publish(A);
     return;
   }
   if (A.on && !(A.guard && A.guard[BCNF_GUARD_HALTED])) {      // (a halted step updates nothing)
-    const AdamScalars as = adam_scalars_of(A, A.asc[0], A.asc[1]);   // (k_fold_splitk published them)
-    reduce_body(L, slab, stride, nwg, dparams, bx - n_gx, smem, &A, &as);
+    reduce_body(L, slab, stride, nwg, dparams, bx - n_sk - 1, smem, &A);
     return;
   }
-  reduce_body(L, slab, stride, nwg, dparams, bx - n_gx, smem);
+  reduce_body(L, slab, stride, nwg, dparams, bx - n_sk - 1, smem);
 }
 
 // Test hook: the whole dynamic LDS of the workgroup set to `value` (bcnf_lds_fill).
@@ -3214,18 +3387,17 @@ int bcnf_backward_tail(const BcnfStackDesc* desc, const void* packed, const void
   G.n_dh = dh ? G.gx_dh * (L.Cp >> 4) : 0;
   G.n_red = (int)((S / 4 + RED_O4 - 1) / RED_O4);
   G.gx_dw = (L.nb + 3) / 4;
-  G.ones = -1;
   const long long n_dw = (long long)G.gx_dw * splits;
   size_t lds = dw1h_lds_bytes(L);
   if (dh_lds_bytes() > lds) lds = dh_lds_bytes();
   const dim3 grid((unsigned)(G.n_dh + G.n_red + n_dw));
   if (vec_rows(L, h)) {
     if ((rc = launch_lds(k_bwd_tail<true>, lds))) return rc;
-    hipLaunchKernelGGL(k_bwd_tail<true>, grid, dim3(BCNF_WG), lds, st, L, L, G, (const float*)packed, d1, h,
+    hipLaunchKernelGGL(k_bwd_tail<true>, grid, dim3(BCNF_WG), lds, st, L, G, (const float*)packed, d1, h,
                        (long long)batch, dh, (const float*)slab, S, nwg, dparams, rps, work);
   } else {
     if ((rc = launch_lds(k_bwd_tail<false>, lds))) return rc;
-    hipLaunchKernelGGL(k_bwd_tail<false>, grid, dim3(BCNF_WG), lds, st, L, L, G, (const float*)packed, d1, h,
+    hipLaunchKernelGGL(k_bwd_tail<false>, grid, dim3(BCNF_WG), lds, st, L, G, (const float*)packed, d1, h,
                        (long long)batch, dh, (const float*)slab, S, nwg, dparams, rps, work);
   }
   if ((rc = check_launch())) return rc;
@@ -3268,7 +3440,8 @@ int bcnf_fold_slab_bytes(const BcnfStackDesc* desc, int32_t in_features, int64_t
   if (!bytes || batch < 0) return BCNF_ERR_ARG;
   const BcnfLayout F = fold_layout(L, in_features, in_features);
   *bytes = ((int64_t)((batch + 15) / 16) * slab_stride_of(L) + w1h_work_floats(F, batch) +
-            (int64_t)L.nb * 16 * F.Cp + 4) * 4;                // + the fused Adam's two scalars (FoldAdamArgs::asc)
+            (int64_t)L.nb * 16 * F.Cp + 4 +                    // + the fused Adam's two scalars (FoldAdamArgs::asc)
+            (int64_t)L.C * (in_features + 1)) * 4;             // + k_fold_tail's copy of [Wf | bf]
   return BCNF_OK;
 }
 
@@ -3424,30 +3597,38 @@ int bcnf_fold_backward_tail(const BcnfStackDesc* desc, const void* packed, const
   A.asc = gx + (long long)L.nb * 16 * F.Cp;
   const int rps = w1h_rows_per_split(batch);
   const long long splits = w1h_splits(batch);
+  float* wf1 = A.asc + 4;                              // [Wf | bf] as k_fold_finish's role a reads them
+  const float* bf1 = feat_bias ? wf1 + (long long)L.C * in_features : nullptr;
   const int n_red = (int)((S / 4 + RED_O4 - 1) / RED_O4);
   const int gx_dw = (L.nb + 1) / 2;
-  const dim3 grid((unsigned)((long long)gx_dw * splits + (A.on ? 1 : 0)));
-  size_t lds = dw1h_lds_bytes(F, 2);
-  if (vec_rows(F, x)) {
-    if ((rc = launch_lds(k_fold_splitk<true>, lds))) return rc;
-    hipLaunchKernelGGL(k_fold_splitk<true>, grid, dim3(BCNF_WG), lds, st, F, d1, x, (long long)batch, rps, work, gx_dw,
-                       (int)in_features, A);
-  } else {
-    if ((rc = launch_lds(k_fold_splitk<false>, lds))) return rc;
-    hipLaunchKernelGGL(k_fold_splitk<false>, grid, dim3(BCNF_WG), lds, st, F, d1, x, (long long)batch, rps, work, gx_dw,
-                       (int)in_features, A);
-  }
+  const long long n_sk = (long long)gx_dw * splits;
+  const dim3 grid((unsigned)(n_sk + 1 + n_red));
+  size_t lds = dw1h_half_lds_bytes(F);
+  if (lds < sizeof(float) * RED_SMEM) lds = sizeof(float) * RED_SMEM;
+  const bool vec = vec_rows(F, x);
+  const bool nt3 = (F.Cp >> 4) <= 6;                   // column tiles per wave: 3 (Xp <= 96: FC_small) or 8
+#define BCNF_FOLD_TAIL(V, NT)                                                                                      \
+  do {                                                                                                             \
+    if ((rc = launch_lds(k_fold_tail<V, NT>, lds))) return rc;                                                     \
+    hipLaunchKernelGGL((k_fold_tail<V, NT>), grid, dim3(BCNF_WG), lds, st, L, F, d1, x, (long long)batch, rps, work, \
+                       gx_dw, (int)n_sk, (int)in_features, (const float*)slab, S, nwg, dparams, feat_weight,       \
+                       feat_bias, wf1, A);                                                                         \
+  } while (0)
+  if (vec && nt3) BCNF_FOLD_TAIL(true, 3);
+  else if (vec) BCNF_FOLD_TAIL(true, 8);
+  else if (nt3) BCNF_FOLD_TAIL(false, 3);
+  else BCNF_FOLD_TAIL(false, 8);
+#undef BCNF_FOLD_TAIL
   if ((rc = check_launch())) return rc;
   const long long total = (long long)L.nb * 16 * F.Cp;
-  const int n_gx = (int)((total + BCNF_WG - 1) / BCNF_WG);
-  hipLaunchKernelGGL(k_red_gx, dim3((unsigned)(n_gx + n_red)), dim3(BCNF_WG), 0, st, L, total, (const float*)work,
-                     (int)splits, gx, n_gx, (const float*)slab, S, nwg, dparams, A);
+  hipLaunchKernelGGL(k_fold_gx, dim3((unsigned)((total + BCNF_WG - 1) / BCNF_WG)), dim3(BCNF_WG), 0, st, total,
+                     (const float*)work, (int)splits, gx);
   if ((rc = check_launch())) return rc;
   const int n_fin = (L.nb + (F.Cp >> 4)) * (L.Cp >> 4);
   size_t fin_lds = sizeof(float) * FIN_SMEM;
   if ((rc = launch_lds(k_fold_finish, fin_lds))) return rc;
   hipLaunchKernelGGL(k_fold_finish, dim3((unsigned)n_fin), dim3(BCNF_WG), fin_lds, st, L, (const float*)packed,
-                     (const float*)gx, feat_weight, feat_bias, (int)in_features, dparams, dfeat_weight, dfeat_bias, A);
+                     (const float*)gx, (const float*)wf1, bf1, (int)in_features, dparams, dfeat_weight, dfeat_bias, A);
   return check_launch();
 }
 

@@ -3,7 +3,7 @@
 //   0 = workgroup-major  slab[w][i]                          (k_backward today: each workgroup's slab contiguous)
 //   1 = chunk-major      slab[i / 64][w][i % 64]             (64-float pieces of every workgroup side by side)
 // k_fill writes the slab the way the backward's helpers do (16-B write-through stores, 1 KB per wave instruction);
-// k_red sums over w with k_red_gx's shape (8 groups x 32 float4, 16 loads in flight per lane, fixed order).
+// k_red sums over w with the slab reduce's shape (reduce_body: 8 groups x 32 float4, 16 loads in flight per lane, fixed order).
 // Built and driven by tools/slab_layout_probe.py; timing only.
 #include <hip/hip_runtime.h>
 

@@ -31,7 +31,7 @@ for wl in ("resim", "sample", "fc_large"):        # other workloads' --stats run
 
 
 def short(name):
-    for k in ("k_forward", "k_backward", "k_inverse", "k_red_gx", "k_fold_splitk", "k_fold_finish", "k_pack_fold",
+    for k in ("k_forward", "k_backward", "k_inverse", "k_fold_tail", "k_fold_gx", "k_fold_finish", "k_pack_fold",
               "k_bwd_tail", "k_adam", "k_clip", "k_pack", "k_hp", "k_resim"):
         if k in name:
             return k
