@@ -1529,8 +1529,14 @@ __device__ __forceinline__ void mlp_forward_s(float* __restrict__ rr, const floa
 #pragma unroll
       for (int q = 0; q < AR::AR4; ++q)
         if (AR::ready_layer(q) == l) emit(q);
+    } else if (DROP) {
+      // training forward that saves nothing (under no_grad): the saving forward's GELU form, not the forward-only
+      // polynomial, so at one (seed, offset) z and log|det J| are the same bits whether or not autograd records
+      float g, dg;
+      gelu_fg(pre, g, dg);
+      a = g * msk[l - 1];
     } else {
-      a = DROP ? gelu_f(pre) * msk[l - 1] : gelu_f(pre);
+      a = gelu_f(pre);
     }
   }
   rf_issue<NH>(rr, R, NH + 1);

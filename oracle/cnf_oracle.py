@@ -71,8 +71,10 @@ def mlp_linear_indices(spec: StackSpec):
     return [i * stride for i in range(n)]
 
 
-def nested_mlp(sd, prefix, spec, y, h, training, gen=None):
-    """ConditionalNestedNeuralNetwork.forward (cnf.py:98-107)."""
+def nested_mlp(sd, prefix, spec, y, h, training, gen=None, keep=None):
+    """ConditionalNestedNeuralNetwork.forward (cnf.py:98-107). Training-mode dropout masks: nn.Dropout's own draw by
+    default, torch.rand masks from `gen`, or masks from outside -- `keep(li)` returns the bool [B, width] keep mask of
+    hidden layer li (the tests feed the HIP kernels' own masks this way)."""
     if spec.n_conditions > 0:
         y = torch.cat([y, h], dim=1)                                  # cnf.py:101
     idx = mlp_linear_indices(spec)
@@ -82,26 +84,33 @@ def nested_mlp(sd, prefix, spec, y, h, training, gen=None):
         if li < len(idx) - 1:
             x = F.gelu(x)                                             # nn.GELU(), approximate='none'
             if spec.dropout > 0.0 and training:
-                if gen is None:
+                if keep is not None:
+                    x = x * keep(li).to(x.dtype) / (1.0 - spec.dropout)
+                elif gen is None:
                     x = F.dropout(x, spec.dropout, True)
                 else:
-                    keep = (torch.rand(x.shape, generator=gen) >= spec.dropout).to(x.dtype)
-                    x = x * keep / (1.0 - spec.dropout)
+                    drawn = (torch.rand(x.shape, generator=gen) >= spec.dropout).to(x.dtype)
+                    x = x * drawn / (1.0 - spec.dropout)
     t, s = x.chunk(2, dim=1)                                          # cnf.py:104
     return t, torch.tanh(s)                                           # cnf.py:107
 
 
-def coupling_forward(sd, prefix, spec, y, h, training=False, gen=None):
-    """ConditionalAffineCouplingLayer.forward (cnf.py:165-196). Returns (z, ldj)."""
+def _half_keep(keep, index, half):
+    return None if keep is None else (lambda li: keep(index, half, li))
+
+
+def coupling_forward(sd, prefix, spec, y, h, training=False, gen=None, keep=None, index=0):
+    """ConditionalAffineCouplingLayer.forward (cnf.py:165-196). Returns (z, ldj). `keep(index, half, li)`: the keep mask
+    of hidden layer li of nn_a (half "a") / nn_b (half "b") of coupling number `index` (see nested_mlp)."""
     if y.dim() == 1:
         y = y.unsqueeze(0)
     if h is not None and h.dim() == 1:
         h = h.unsqueeze(0)
     ya, yb = y.chunk(2, dim=-1)
-    t_a, s_a = nested_mlp(sd, prefix + ".nn_a", spec, ya, h, training, gen)
+    t_a, s_a = nested_mlp(sd, prefix + ".nn_a", spec, ya, h, training, gen, _half_keep(keep, index, "a"))
     zb = torch.exp(s_a) * yb + t_a
     if spec.two_way:
-        t_b, s_b = nested_mlp(sd, prefix + ".nn_b", spec, zb, h, training, gen)
+        t_b, s_b = nested_mlp(sd, prefix + ".nn_b", spec, zb, h, training, gen, _half_keep(keep, index, "b"))
         za = torch.exp(s_b) * ya + t_b
     else:
         za = ya
@@ -111,13 +120,13 @@ def coupling_forward(sd, prefix, spec, y, h, training=False, gen=None):
     return torch.cat([za, zb], dim=-1), ldj
 
 
-def coupling_inverse(sd, prefix, spec, z, h, training=False, gen=None):
+def coupling_inverse(sd, prefix, spec, z, h, training=False, gen=None, keep=None, index=0):
     """ConditionalAffineCouplingLayer.inverse (cnf.py:198-213) — bug-compatible for two_way."""
     za, zb = z.chunk(2, dim=-1)
-    t_a, s_a = nested_mlp(sd, prefix + ".nn_a", spec, za, h, training, gen)
+    t_a, s_a = nested_mlp(sd, prefix + ".nn_a", spec, za, h, training, gen, _half_keep(keep, index, "a"))
     yb = (zb - t_a) * torch.exp(-s_a)
     if spec.two_way:
-        t_b, s_b = nested_mlp(sd, prefix + ".nn_b", spec, yb, h, training, gen)
+        t_b, s_b = nested_mlp(sd, prefix + ".nn_b", spec, yb, h, training, gen, _half_keep(keep, index, "b"))
         ya = (za - t_b) * torch.exp(-s_b)
     else:
         ya = za
@@ -157,17 +166,19 @@ def lstm_feature_forward(sd, spec, cond, prefix="feature_network_stack.feature_n
     return x.mean(dim=pool_dim)
 
 
-def model_forward(sd, spec, y, h, training=False, gen=None):
-    """CondRealNVP_v2.forward layer loop (cnf.py:476-488) given features h. Returns (z, ldj)."""
+def model_forward(sd, spec, y, h, training=False, gen=None, keep=None):
+    """CondRealNVP_v2.forward layer loop (cnf.py:476-488) given features h. Returns (z, ldj). `keep`: dropout masks from
+    outside, called as keep(coupling number 0..n_blocks-1, "a" / "b", hidden-layer index) (see nested_mlp)."""
     ldj = torch.zeros(y.shape[0], dtype=y.dtype)
-    for li, kind in enumerate(layer_kinds(spec)):
+    kinds = layer_kinds(spec)
+    for li, kind in enumerate(kinds):
         p = f"layers.{li}"
         if kind == "actnorm":
             scale, bias = sd[p + ".scale"], sd[p + ".bias"]
             y = scale * y + bias                                      # cnf.py:349
             ldj = ldj + torch.sum(torch.log(torch.abs(scale)), dim=-1)  # cnf.py:350
         elif kind == "coupling":
-            y, l = coupling_forward(sd, p, spec, y, h, training, gen)
+            y, l = coupling_forward(sd, p, spec, y, h, training, gen, keep, kinds[:li].count("coupling"))
             ldj = ldj + l
         else:
             y = y @ sd[p + ".orthonormal_matrix"]                     # cnf.py:335
@@ -175,8 +186,8 @@ def model_forward(sd, spec, y, h, training=False, gen=None):
     return y, ldj
 
 
-def model_inverse(sd, spec, z, h, training=False, gen=None):
-    """CondRealNVP_v2.inverse (cnf.py:495-508) given features h."""
+def model_inverse(sd, spec, z, h, training=False, gen=None, keep=None):
+    """CondRealNVP_v2.inverse (cnf.py:495-508) given features h. `keep` as in model_forward."""
     kinds = layer_kinds(spec)
     for li in reversed(range(len(kinds))):
         p = f"layers.{li}"
@@ -184,7 +195,7 @@ def model_inverse(sd, spec, z, h, training=False, gen=None):
         if kind == "actnorm":
             z = (z - sd[p + ".bias"]) / sd[p + ".scale"]              # cnf.py:353-354
         elif kind == "coupling":
-            z = coupling_inverse(sd, p, spec, z, h, training, gen)
+            z = coupling_inverse(sd, p, spec, z, h, training, gen, keep, kinds[:li].count("coupling"))
         else:
             z = z @ sd[p + ".orthonormal_matrix"].T                   # cnf.py:339
     return z
@@ -203,8 +214,17 @@ def log_prob(z, ldj):
     return -inn_nll_loss(z, ldj, reduction="none") - 0.5 * D * math.log(2.0 * math.pi)
 
 
-def sample(sd, spec, n_samples, cond, sigma=1.0, outer=False, batch_size=100, sample_batch_size=None):
-    """CondRealNVP_v2.sample / _sample (cnf.py:510-588), 2-D conditions, CPU generator stream."""
+def sample(sd, spec, n_samples, cond, sigma=1.0, outer=False, batch_size=100, sample_batch_size=None, keeps=None):
+    """CondRealNVP_v2.sample / _sample (cnf.py:510-588), 2-D conditions, CPU generator stream. `keeps` (a model left
+    in train mode): keeps(n, rows) returns the `keep` callable of the n-th inverse call (rows latents), else eval."""
+    n_inv = 0
+
+    def inverse(z, h):
+        nonlocal n_inv
+        keep = None if keeps is None else keeps(n_inv, z.shape[0])
+        n_inv += 1
+        return model_inverse(sd, spec, z, h, training=keep is not None, keep=keep)
+
     if sample_batch_size is None:
         sample_batch_size = batch_size
     m_sizes = [sample_batch_size] * (n_samples // sample_batch_size) + [n_samples % sample_batch_size]
@@ -221,11 +241,11 @@ def sample(sd, spec, n_samples, cond, sigma=1.0, outer=False, batch_size=100, sa
                     z = sigma * torch.randn(m * nc, spec.size)          # cnf.py:578
                     rc = c.repeat(m, *([1] * (c.ndim - 1)))            # cnf.py:579
                     h = feature_forward(sd, spec, rc)
-                    rows[-1].append(model_inverse(sd, spec, z, h).view(m, nc, spec.size))
+                    rows[-1].append(inverse(z, h).view(m, nc, spec.size))
                 else:
                     z = sigma * torch.randn(m, spec.size)              # cnf.py:584
                     h = feature_forward(sd, spec, c)
-                    rows[-1].append(model_inverse(sd, spec, z, h).view(m, spec.size))
+                    rows[-1].append(inverse(z, h).view(m, spec.size))
     return torch.cat([torch.cat(r, dim=0) for r in rows], dim=1)
 
 

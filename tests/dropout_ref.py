@@ -1,9 +1,10 @@
 """Test-side restatement of the FC_small kernels' dropout draw (bcnf_device.h: philox4x32_10, dropout_bits), numpy.
 
 Not the reference's RNG: the reference draws nn.Dropout masks with torch's generator (cnf.py:82-83), which no
-in-kernel generator can reproduce, so training parity is statistical plus exact fused == unfused equality on one
-stream. This module pins the kernel's own stream bit for bit: Philox4x32-10 (Salmon et al. 2011, checked
-against the Random123 known-answer vectors in tests/test_dropout_rule.py) and the keep rule "u32 >= round(p 2^32)".
+in-kernel generator can reproduce, so training parity is gated against the fp64 oracle fed the kernels' own masks
+(keep_callable below hands them over). This module pins the kernel's own stream bit for bit:
+Philox4x32-10 (Salmon et al. 2011, checked against the Random123 known-answer vectors in tests/test_dropout_rule.py)
+and the keep rule "u32 >= round(p 2^32)".
 """
 import numpy as np
 
@@ -57,3 +58,45 @@ def keep_bits(p, seed, offset, sample, block, lane, tag=0, nu=7):
         u = (hi[i] << np.uint64(16)) | lo[i]
         bits |= (u >= t).astype(np.uint32) << np.uint32(i)
     return bits
+
+
+def launch_sample(batch, workgroups=None):
+    """Sample index dropout_bits sees per launch row (k_forward / k_inverse: bc = min(b, B - 1)): rows past the batch
+    in the last 16-sample workgroup replay the last sample, masks included."""
+    rows = batch if workgroups is None else 16 * workgroups
+    return np.minimum(np.arange(rows), batch - 1)
+
+
+def keep_callable(p, seed, offset, n_blocks, hidden, batch, tag=0):
+    """The oracle's `keep` callable (oracle/cnf_oracle.py: model_forward / model_inverse) for one small-family launch:
+    keep(k, "a", li) = bool [batch, hidden[li]], unit (sample b, block k, lane j, hidden layer li + 1) of keep_bits.
+    The counter is (sample = launch row, block = coupling number, lane = hidden unit j of the 16-lane row layout);
+    tag 0 for k_forward, 0x40000000 for the training-mode k_inverse. The small family has no two_way couplings."""
+    import torch
+    hidden = list(hidden)
+    bits = keep_bits(p, seed, offset, launch_sample(batch)[None, :, None], np.arange(n_blocks)[:, None, None],
+                     np.arange(16)[None, None, :], tag=tag, nu=len(hidden))          # [block][sample][lane]
+
+    def keep(k, half, li):
+        assert half == "a" and 0 <= k < n_blocks and 0 <= li < len(hidden)
+        return torch.from_numpy(((bits[k, :, :hidden[li]] >> np.uint32(li)) & np.uint32(1)).astype(bool))
+    return keep
+
+
+# The small-family (register-resident k_forward / k_backward / k_inverse) shapes the training-parity tests use besides
+# FC_small: NH = 8 (the second-draw path), hidden widths below 16 with NH = 2 and no ActNorm, NH = 1 with a padded C,
+# NH = 8 with width 4.
+SMALL_TRAIN_SHAPES = {
+    "nh8_p50": dict(size=19, nested_sizes=[16] * 8, n_blocks=3, n_conditions=80, dropout=0.5, act_norm=True),
+    "d7_h12_9": dict(size=7, nested_sizes=[12, 9], n_blocks=3, n_conditions=5, dropout=0.1, act_norm=False),
+    "d32_nh1": dict(size=32, nested_sizes=[16], n_blocks=2, n_conditions=120, dropout=0.25, act_norm=True),
+    "d2_h4x8": dict(size=2, nested_sizes=[4] * 8, n_blocks=5, n_conditions=3, dropout=0.3, act_norm=True),
+}
+
+
+def shape_config(shape):
+    """from_config dict of a coupling stack fed its condition directly (ConcatenateCondition only: h = the condition)."""
+    return {"global": {"parameter_selection": [f"p{i}" for i in range(shape["size"])]},
+            "model": {"kwargs": dict(shape)},
+            "feature_networks": [{"type": "ConcatenateCondition",
+                                  "kwargs": {"input_size": None, "output_size": shape["n_conditions"]}}]}

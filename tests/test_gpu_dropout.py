@@ -54,3 +54,55 @@ def test_forward_dropout_masks_follow_the_32bit_rule(p, NH):
     assert abs(drops - lam) < 4 * np.sqrt(lam * (1 - p)) + 1, (drops, lam)
     if p < 2.0**-17:
         assert drops > 0          # the 16-bit rule's threshold was 0 here: no unit ever dropped
+
+
+def _small_train_cases():
+    from dropout_ref import SMALL_TRAIN_SHAPES, shape_config
+    cases = {"fc_small": FC_SMALL_CFG}
+    cases.update({k: shape_config(v) for k, v in SMALL_TRAIN_SHAPES.items()})
+    return cases
+
+
+@pytest.mark.parametrize("case", ["fc_small", "nh8_p50", "d7_h12_9", "d32_nh1", "d2_h4x8"])
+def test_forward_dropout_masks_at_the_parity_shapes(case):
+    """The record check at the shapes tests/test_gpu_train_parity.py feeds to the oracle (hidden widths below 16,
+    NH = 1, 2, 7, 8), ragged B = 37: every unit of the real lanes of all 16 rows of each workgroup, the 11 rows past
+    the batch included (they replay sample B - 1, masks and all). Records: [k][workgroup][AR4][256 threads] float4,
+    AR4 = (2 NH + 3) / 4, floats (activation, derivative) of hidden layers 1..NH first (ActRec, bcnf_stack.hip)."""
+    from bcnf_amd import CondRealNVP_v2
+    from dropout_ref import launch_sample
+    cfg = _small_train_cases()[case]
+    kw = cfg["model"]["kwargs"]
+    hidden, nb, p, C = kw["nested_sizes"], kw["n_blocks"], kw["dropout"], kw["n_conditions"]
+    NH = len(hidden)
+    torch.manual_seed(0)
+    m = CondRealNVP_v2.from_config(cfg).to("cuda").train()
+    st = m.fused
+    assert type(st).__name__ == "FusedStack"
+    st.set_seed(0xC0FFEE1234)
+    st.rng_state()[1] = 5
+    B = 37
+    nwg, AR4 = (B + 15) // 16, (2 * NH + 3) // 4
+    g = torch.Generator().manual_seed(3)
+    y = torch.randn(B, kw["size"], generator=g).cuda()
+    h = torch.randn(B, C, generator=g).cuda()
+    seed, off = (int(v) for v in st.rng_state().tolist())
+    with torch.no_grad():
+        _, _, _, (ws, _) = st.launch_forward(y, h, True, save=True)
+    torch.cuda.synchronize()
+    assert int(st.rng_state()[1].item()) == off + 1
+    rec = ws[: nb * nwg * AR4 * 1024].view(nb, nwg, AR4, 256, 4).permute(0, 1, 3, 2, 4).reshape(nb, nwg, 256, 4 * AR4)
+    got = (rec[..., 1:2 * NH:2] != 0).cpu().numpy()
+    t = np.arange(256)
+    row = np.arange(nwg)[:, None] * 16 + _sample_of(t)[None, :]
+    sample = launch_sample(B, nwg)[row]
+    lane = (t & 15)[None, None, :]
+    bits = keep_bits(p, seed, off, sample[None], np.arange(nb)[:, None, None], lane, nu=NH)
+    want = ((bits[..., None] >> np.arange(NH, dtype=np.uint32)) & 1).astype(bool)
+    real = np.broadcast_to(lane[..., None] < np.asarray(hidden)[None, None, None, :], want.shape)
+    assert got.shape == want.shape
+    assert np.array_equal(got[real], want[real]), int((got != want)[real].sum())
+    real = real & (row < B)[None, :, :, None]             # the keep rate over independent draws only
+    n = int(real.sum())
+    drops = n - int(want[real].sum())
+    assert abs(drops - p * n) < 4 * np.sqrt(n * p * (1 - p)) + 1, (drops, p * n)
