@@ -7,6 +7,7 @@ from bcnf_amd.cnf import (ActNorm, CondRealNVP_v2, ConditionalAffineCouplingLaye
                           ConditionalNestedNeuralNetwork, InvertibleLayer, OrthonormalTransformation)
 from bcnf_amd.feature_network import (ConcatenateCondition, FeatureNetwork, FeatureNetworkStack,
                                       FullyConnectedFeatureNetwork, LSTMFeatureNetwork)
+from bcnf_amd.sampling import posterior_mode
 from bcnf_amd.utils import ParameterIndexMapping, inn_nll_loss, load_config, log_prob_from_latent
 
 __all__ = [
@@ -14,4 +15,5 @@ __all__ = [
     "ConditionalNestedNeuralNetwork", "InvertibleLayer", "OrthonormalTransformation", "ConcatenateCondition",
     "FeatureNetwork", "FeatureNetworkStack", "FullyConnectedFeatureNetwork", "LSTMFeatureNetwork",
     "ParameterIndexMapping", "inn_nll_loss", "load_config", "log_prob_from_latent",
+    "posterior_mode",
 ]

@@ -42,6 +42,7 @@ EXPORTS = (
     "bcnf_wide_gemm_test", "bcnf_wide_backward_plan", "bcnf_rank_count", "bcnf_resimulate",
     "bcnf_guard_check_global", "bcnf_abi_version",
     "bcnf_head_work_bytes", "bcnf_head_mse_forward", "bcnf_head_mse_backward", "bcnf_hybrid_finalize",
+    "bcnf_stack_inverse_logdet", "bcnf_wide_inverse_logdet",
 )
 ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
 MAX_TENSORS = 48
@@ -141,6 +142,7 @@ def _bind(lib):
         "bcnf_stack_forward": (_i32, [_pdesc, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
         "bcnf_stack_backward": (_i32, [_pdesc, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
         "bcnf_stack_inverse": (_i32, [_pdesc, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+        "bcnf_stack_inverse_logdet": (_i32, [_pdesc, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
         "bcnf_grad_reduce": (_i32, [_pdesc, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
         "bcnf_nll_forward": (_i32, [_pdesc, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
         "bcnf_nll_backward": (_i32, [_pdesc, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -193,6 +195,7 @@ def _bind(lib):
         "bcnf_wide_backward": (_i32, [_pdesc, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp,
                                       _vp]),
         "bcnf_wide_inverse": (_i32, [_pdesc, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+        "bcnf_wide_inverse_logdet": (_i32, [_pdesc, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
         "bcnf_rank_count": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
         "bcnf_resimulate": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _i32, ctypes.c_double, _i32,
                                    ctypes.c_double, ctypes.c_double, _i32, _vp, _vp, _vp, _vp]),

@@ -236,16 +236,21 @@ class ConditionalAffineCouplingLayer(ConditionalInvertibleLayer):
             z_a = y_a
         return torch.cat([z_a, z_b], dim=-1), ldj
 
-    def layerwise_inverse(self, z: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    def layerwise_inverse(self, z: torch.Tensor, y: torch.Tensor, want_ldj: bool = False):
+        """want_ldj (one-way only): also the forward's log|det J| of this coupling at the returned value -- the
+        identity half passes through, so log_s_a here is the forward's."""
         z_a, z_b = z.chunk(2, dim=-1)
         t_a, log_s_a = self.nn_a(z_a, y)
         y_b = (z_b - t_a) * torch.exp(-log_s_a)
         if self.two_way:
+            if want_ldj:
+                raise ValueError("bcnf_amd: no log-density for two_way couplings")
             t_b, log_s_b = self.nn_b(y_b, y)        # the reference's two_way inverse, as written (cnf.py:206-208)
             y_a = (z_a - t_b) * torch.exp(-log_s_b)
         else:
             y_a = z_a
-        return torch.cat([y_a, y_b], dim=-1)
+        out = torch.cat([y_a, y_b], dim=-1)
+        return (out, log_s_a.sum(dim=-1)) if want_ldj else out
 
 
 class OrthonormalTransformation(ConditionalInvertibleLayer):
@@ -650,44 +655,93 @@ class CondRealNVP_v2(ConditionalInvertibleLayer):
         z = self.forward(y, *conditions, log_det_J=True)
         return log_prob_from_latent(z, self.log_det_J)
 
-    def inverse(self, z: torch.Tensor, *conditions: torch.Tensor) -> torch.Tensor:
-        self._check_supported()
-        condition = self.feature_network_stack(*conditions)
-        if self._path == "layerwise":
-            return self._fused.inverse(z, condition)
-        return stack_inverse(self._fused, z, condition, training=self.training)
+    def _check_log_density(self):
+        """The density of a draw is defined only where the inverse is the forward's inverse and deterministic.
+        Raises before any launch."""
+        if self.two_way:
+            raise ValueError("bcnf_amd: no log-density for a two_way model: the reference's two_way inverse "
+                             "(cnf.py:198-213), which this package reproduces, is not the inverse of its forward")
+        if self.training and self.dropout > 0:
+            raise ValueError("bcnf_amd: no log-density for a model in train mode with dropout > 0 (the draw is not "
+                             "deterministic); call model.eval() first")
 
-    def _inverse_indexed(self, z, h_unique, cond_index):
+    def inverse(self, z: torch.Tensor, *conditions: torch.Tensor, log_det_J: bool = False) -> torch.Tensor:
+        """cnf.py:499-506. log_det_J=True also sets self.log_det_J (N,) = log|det dz/dy| at the returned y -- the
+        value forward(y, *conditions, log_det_J=True) leaves there -- from the same launch (one-way, eval)."""
+        self._check_supported()
+        if log_det_J:
+            self._check_log_density()
+        condition = self.feature_network_stack(*conditions)
+        if not log_det_J:
+            if self._path == "layerwise":
+                return self._fused.inverse(z, condition)
+            return stack_inverse(self._fused, z, condition, training=self.training)
+        if z.dim() == 1:
+            z = z.unsqueeze(0)
         if self._path == "layerwise":
-            return self._fused.inverse(z, h_unique[cond_index])
-        return stack_inverse(self._fused, z, h_unique, cond_index=cond_index, training=self.training)
+            y, ldj, _ = self._fused.inverse(z, condition, want_ldj=True)
+        else:
+            y, ldj, _ = stack_inverse(self._fused, z, condition, training=self.training, want_ldj=True)
+        self.log_det_J = ldj
+        return y
+
+    def _inverse_indexed(self, z, h_unique, cond_index, want_ldj: bool = False):
+        """want_ldj=True: (y, log_prob) of the rows."""
+        if self._path == "layerwise":
+            out = self._fused.inverse(z, h_unique[cond_index], want_ldj=want_ldj)
+        else:
+            out = stack_inverse(self._fused, z, h_unique, cond_index=cond_index, training=self.training,
+                                want_ldj=want_ldj)
+        return (out[0], out[2]) if want_ldj else out
 
     def sample(self, n_samples: int, *conditions: torch.Tensor, sigma: float = 1, outer: bool = False,
                batch_size: int = 100, sample_batch_size: int | None = None, output_device: str = "cpu",
-               verbose: bool = False) -> torch.Tensor:
-        """cnf.py:510-538: same chunking, same CPU-generator z stream, same output layout."""
+               verbose: bool = False, return_log_prob: bool = False):
+        """cnf.py:510-538: same chunking, same CPU-generator z stream, same output layout.
+        return_log_prob=True: (samples, log_prob) with log_prob = log p(sample | condition) under the model, shape
+        (n, N) for outer=True and (n,) otherwise, on output_device; it comes out of the inverse launch (no second
+        pass) and the samples are bit-identical to the plain call's. For sigma != 1 the density of the PROPOSAL the
+        draws come from is  log_prob + 0.5 |z|^2 (1 - 1/sigma^2) - D log sigma  with z the (scaled) latent."""
         self._check_supported()
+        if return_log_prob:
+            self._check_log_density()
         if sample_batch_size is None:
             sample_batch_size = batch_size
         m_sizes = [sample_batch_size] * (n_samples // sample_batch_size) + [n_samples % sample_batch_size]
         rows: list[list[torch.Tensor]] = []
+        lps: list[list[torch.Tensor]] = []
         with torch.no_grad(), self._fused.reuse_pack():
             for b in range(0, len(conditions[0]), batch_size):
                 batch_conditions = [c[b: b + batch_size].to(self.device) for c in conditions]
                 rows.append([])
+                lps.append([])
                 for m in m_sizes:
                     if m == 0:
                         continue
-                    rows[-1].append(self._sample(m, *batch_conditions, outer=outer, sigma=sigma).to(output_device))
-        return torch.cat([torch.cat(r, dim=0) for r in rows], dim=1)
+                    out = self._sample(m, *batch_conditions, outer=outer, sigma=sigma, want_lp=return_log_prob)
+                    if return_log_prob:
+                        lps[-1].append(out[1].to(output_device))
+                        out = out[0]
+                    rows[-1].append(out.to(output_device))
+        samples = torch.cat([torch.cat(r, dim=0) for r in rows], dim=1)
+        if not return_log_prob:
+            return samples
+        lp = [torch.cat(r, dim=0) for r in lps]       # per condition chunk: (n, N_chunk) for outer, else (n,)
+        return samples, torch.cat(lp, dim=1 if lp[0].dim() > 1 else 0)
 
-    def _sample(self, n_samples: int, *conditions: torch.Tensor, sigma: float = 1, outer: bool = False):
-        """cnf.py:540-588. Features are computed once per distinct condition; tiled rows index them."""
+    def _sample(self, n_samples: int, *conditions: torch.Tensor, sigma: float = 1, outer: bool = False,
+                want_lp: bool = False):
+        """cnf.py:540-588. Features are computed once per distinct condition; tiled rows index them.
+        want_lp: (samples, log_prob) with log_prob shaped as the samples without their last axis."""
+        def shaped(out, *shape):
+            if want_lp:
+                return out[0].view(*shape, self.size), out[1].view(*shape)
+            return out.view(*shape, self.size)
         if all(c.ndim == 1 for c in conditions):
             z = (sigma * torch.randn(n_samples, self.size)).to(self.device)
             h = self.feature_network_stack(*[c.unsqueeze(0) for c in conditions])
             idx = torch.zeros(n_samples, dtype=torch.int64, device=z.device)
-            return self._inverse_indexed(z, h, idx).view(n_samples, self.size)
+            return shaped(self._inverse_indexed(z, h, idx, want_lp), n_samples)
         if all(c.ndim > 1 for c in conditions):
             if outer:
                 if len(set(c.shape[0] for c in conditions)) != 1:
@@ -697,9 +751,15 @@ class CondRealNVP_v2(ConditionalInvertibleLayer):
                 z = (sigma * torch.randn(n_samples * nc, self.size)).to(self.device)
                 h = self.feature_network_stack(*conditions)
                 idx = torch.arange(n_samples * nc, device=z.device, dtype=torch.int64) % nc
-                return self._inverse_indexed(z, h, idx).view(n_samples, nc, self.size)
+                return shaped(self._inverse_indexed(z, h, idx, want_lp), n_samples, nc)
             z = (sigma * torch.randn(n_samples, self.size)).to(self.device)
             h = self.feature_network_stack(*conditions)
+            if want_lp:
+                if self._path == "layerwise":
+                    y, _, lp = self._fused.inverse(z, h, want_ldj=True)
+                else:
+                    y, _, lp = stack_inverse(self._fused, z, h, training=self.training, want_ldj=True)
+                return shaped((y, lp), n_samples)
             if self._path == "layerwise":
                 return self._fused.inverse(z, h).view(n_samples, self.size)
             return stack_inverse(self._fused, z, h, training=self.training).view(n_samples, self.size)
@@ -735,15 +795,27 @@ class _LayerwiseStack:
                 y = y @ layer.orthonormal_matrix
         return y, ldj
 
-    def inverse(self, z: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+    def inverse(self, z: torch.Tensor, h: torch.Tensor, want_ldj: bool = False):
+        """want_ldj=True (one-way, deterministic): (y, ldj, log_prob) as FusedStack.launch_inverse -- the same running
+        sum of the couplings' log-scales and the ActNorm constants, with torch ops."""
         self._check(z)
+        z_in = z
+        ldj = torch.zeros(z.shape[0], dtype=z.dtype, device=z.device) if want_ldj else None
         for layer in reversed(self._model.layers):
             if isinstance(layer, ActNorm):
                 z = layer.inverse(z)
+                if want_ldj:
+                    ldj = ldj + torch.sum(torch.log(torch.abs(layer.scale)), dim=-1)
             elif isinstance(layer, ConditionalAffineCouplingLayer):
-                z = layer.layerwise_inverse(z, h)
+                if want_ldj:
+                    z, l = layer.layerwise_inverse(z, h, want_ldj=True)
+                    ldj = ldj + l
+                else:
+                    z = layer.layerwise_inverse(z, h)
             else:
                 z = z @ layer.orthonormal_matrix.T
+        if want_ldj:
+            return z, ldj, log_prob_from_latent(z_in, ldj)
         return z
 
     def reuse_pack(self):

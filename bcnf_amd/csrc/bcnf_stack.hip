@@ -2422,15 +2422,23 @@ __device__ __forceinline__ void inv_mv_mo(floatx4 (&acc)[G], const float* __rest
   }
 }
 
+__device__ __forceinline__ float sum_rows4(float v);
+
 // PERM (D_a, D_b <= 12): the y / z half-vectors hold feature 3q + r in register r < 3 of lane (q, s) (register 3
 // stays 0), so every product with a half-vector input contracts in 3 MFMA steps instead of 4 (mix 16 -> 12 and
 // Linear 1 4 -> 3 MFMAs per block) and the coupling / ActNorm inverse runs on 3 registers. Rows of a permuted
 // output with no feature read entry 0 of lane record 15, which is zero in the mix, T and S rows when D_a, D_b < 15.
-template <int NH, bool PERM>
+// LDJ: also the forward's log|det J| at the returned y (and log_prob of it). A one-way coupling's inverse passes the
+// identity half through, so the S = tanh(s') it forms at block k IS the forward's S at y: each lane keeps the running
+// sum of S over its valid features (registers in order, blocks nb - 1 .. 0), the four 16-lane rows are added once
+// after the loop (sum_rows4), then the packed ActNorm constant; |z|^2 comes from the prologue's z loads the same way.
+template <int NH, bool PERM, bool LDJ = false>
 __global__ __launch_bounds__(INV_M_WG, PERM ? INV_M_OCC - 1 : INV_M_OCC) void k_inverse_mfma(BcnfLayout L, const float* __restrict__ pk,
                                                           const float* __restrict__ zin, const float* __restrict__ hp,
                                                           long long R, const int64_t* __restrict__ cond_index,
-                                                          long long N, float* __restrict__ yout) {
+                                                          long long N, float* __restrict__ yout,
+                                                          float* __restrict__ ldj_out = nullptr,
+                                                          float* __restrict__ logp_out = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   using F = RecF<NH>;
   constexpr int G = INV_M_G;
@@ -2449,17 +2457,27 @@ __global__ __launch_bounds__(INV_M_WG, PERM ? INV_M_OCC - 1 : INV_M_OCC) void k_
   // half-vector feature of register r (15: none -- a zero row of the mix / T / S records)
   auto feat = [&](int r) { return PERM ? (r < 3 ? 3 * q + r : 15) : 4 * q + r; };
   floatx4 ya[G], yb[G];
+  float ls[G];                                      // LDJ: the lane's sum of S over its valid features
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     b[g] = (long long)blockIdx.x * INV_M_SPB + (threadIdx.x >> 6) * INV_M_SPW + 16 * g + s;
     const long long bc = b[g] < N ? b[g] : N - 1;
     const long long hr = cond_index ? (long long)cond_index[bc] : bc;
     hpl[g] = reinterpret_cast<const floatx4*>(hp + hr * 16 + 4 * q);   // HP[k][hr][4q..4q+3]
+    ls[g] = 0.f;
+    float zz = 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int f = feat(r);
       ya[g][r] = (f < Da) ? zin[bc * D + f] : 0.f;
       yb[g][r] = (f < Db) ? zin[bc * D + Da + f] : 0.f;
+      if (LDJ) zz += ya[g][r] * ya[g][r] + yb[g][r] * yb[g][r];
+    }
+    if (LDJ && logp_out) {
+      // log_prob's latent term now, while z is in registers; the epilogue adds ldj to it (the same lane stores and
+      // reloads it, so no register stays live across the coupling loop for it)
+      const float q2 = sum_rows4(zz);
+      if (q == 0 && b[g] < N) logp_out[b[g]] = -0.5f * q2 - 0.5f * (float)D * 1.8378770664093454836f;
     }
   }
 
@@ -2537,6 +2555,7 @@ __global__ __launch_bounds__(INV_M_WG, PERM ? INV_M_OCC - 1 : INV_M_OCC) void k_
       for (int g = 0; g < G; ++g) {
         const float S = tanh_bf(Sp[g][r]);
         const float ybn = (zb[g][r] - T[g][r]) * exp_fast(-S);                    // cnf.py:205
+        if (LDJ) ls[g] += (f < Db) ? S : 0.f;                                      // cnf.py:190 at the returned y
         ya[g][r] = (f < Da) ? (za[g][r] - an[1]) * an[0] : 0.f;                    // ActNorm inverse (cnf.py:353-354)
         yb[g][r] = (f < Db) ? (ybn - an[3]) * an[2] : 0.f;
       }
@@ -2552,6 +2571,17 @@ __global__ __launch_bounds__(INV_M_WG, PERM ? INV_M_OCC - 1 : INV_M_OCC) void k_
         const int f = feat(r);
         if (f < Da) yout[b[g] * D + f] = ya[g][r];
         if (f < Db) yout[b[g] * D + Da + f] = yb[g][r];
+      }
+    }
+  }
+  if (LDJ) {
+    const float ldc = pk[L.ldc_off];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float ltot = sum_rows4(ls[g]) + ldc;
+      if (q == 0 && b[g] < N) {
+        ldj_out[b[g]] = ltot;
+        if (logp_out) logp_out[b[g]] += ltot;
       }
     }
   }
@@ -3196,6 +3226,29 @@ int inv_dispatch(const BcnfLayout& L, const float* pk, const float* zin, const f
   return check_launch();
 }
 
+// The eval inverse that also returns the forward's log|det J| at y (and log_prob): matrix-core layouts only -- every
+// layout layout_supported admits takes k_inverse_mfma in eval; one that would not is reported, not served by a
+// second implementation.
+template <int NH>
+int inv_ldj_dispatch(const BcnfLayout& L, const float* pk, const float* zin, const float* hp, long long R,
+                     const int64_t* ci, long long N, float* y, float* ldj, float* logp, hipStream_t st) {
+  if (!layout_matches<NH>(L)) return BCNF_ERR_ARG;
+  if (L.RF != inv_m_rf<NH>() || L.PMB != (NH + 6) * 256 + (NH - 1) * 16 + 96) return BCNF_ERR_UNSUPPORTED;
+  int rc;
+  size_t lds_m = sizeof(float) * (size_t)(2 * RING);
+  const dim3 grid_m((unsigned)((N + INV_M_SPB - 1) / INV_M_SPB));
+  if (L.Da <= 12 && L.Db <= 12) {
+    if ((rc = launch_lds(k_inverse_mfma<NH, true, true>, lds_m))) return rc;
+    hipLaunchKernelGGL((k_inverse_mfma<NH, true, true>), grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y,
+                       ldj, logp);
+  } else {
+    if ((rc = launch_lds(k_inverse_mfma<NH, false, true>, lds_m))) return rc;
+    hipLaunchKernelGGL((k_inverse_mfma<NH, false, true>), grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y,
+                       ldj, logp);
+  }
+  return check_launch();
+}
+
 long long slab_stride_of(const BcnfLayout& L) { return (long long)L.nb * L.sblk; }
 
 template <int NH>
@@ -3678,6 +3731,31 @@ int bcnf_stack_inverse(const BcnfStackDesc* desc, const void* packed, const floa
   if ((rc = launch_hp(L, pk, h, h_rows, hp, st))) return rc;
   switch (L.NH) {
 #define BCNF_CASE(N) case N: return inv_dispatch<N>(L, pk, z, hp, h_rows, cond_index, n_rows, y, drop, rng_state, st);
+    BCNF_CASE(1) BCNF_CASE(2) BCNF_CASE(3) BCNF_CASE(4) BCNF_CASE(5) BCNF_CASE(6) BCNF_CASE(7) BCNF_CASE(8)
+#undef BCNF_CASE
+    default: return BCNF_ERR_UNSUPPORTED;
+  }
+}
+
+int bcnf_stack_inverse_logdet(const BcnfStackDesc* desc, const void* packed, const float* z, const float* h,
+                              int64_t h_rows, const int64_t* cond_index, int64_t n_rows, float* y, float* ldj,
+                              float* log_prob, void* scratch, void* stream) {
+  if (!desc) return BCNF_ERR_ARG;
+  if (desc->two_way) return BCNF_ERR_UNSUPPORTED;   // the reference's two_way inverse is not its forward's inverse
+  if (!y || !ldj) return BCNF_ERR_ARG;
+  BcnfLayout L;
+  int rc = make_layout(desc, &L);
+  if (rc) return rc;
+  if (!layout_supported(L, desc)) return BCNF_ERR_UNSUPPORTED;
+  if (n_rows == 0) return BCNF_OK;
+  if (n_rows < 0 || h_rows < 1 || !packed || !z || !h || !scratch) return BCNF_ERR_ARG;
+  if (!cond_index && h_rows != n_rows) return BCNF_ERR_ARG;
+  const float* pk = (const float*)packed;
+  hipStream_t st = (hipStream_t)stream;
+  float* hp = (float*)scratch;
+  if ((rc = launch_hp(L, pk, h, h_rows, hp, st))) return rc;
+  switch (L.NH) {
+#define BCNF_CASE(N) case N: return inv_ldj_dispatch<N>(L, pk, z, hp, h_rows, cond_index, n_rows, y, ldj, log_prob, st);
     BCNF_CASE(1) BCNF_CASE(2) BCNF_CASE(3) BCNF_CASE(4) BCNF_CASE(5) BCNF_CASE(6) BCNF_CASE(7) BCNF_CASE(8)
 #undef BCNF_CASE
     default: return BCNF_ERR_UNSUPPORTED;

@@ -1379,6 +1379,7 @@ struct LinkArgs {
   float* U;                     // forward save: [u_in | 1 | 0] of block vh [B][UP] (nullable)
   const uint64_t* rng;          // dropout (nullable = off)
   unsigned long long* dbg;      // phase timestamps of workgroup 0 (bcnf_wide_debug_phases), nullable
+  float* logp;                  // inverse with ldj != nullptr (one-way stacks), block 0's tail: log_prob per row (nullable)
 };
 
 // Phase stamps of the forward link: diagnostic build only (-DBCNF_PHASE_STAMPS, tools/exp_variants.sh).
@@ -1414,9 +1415,14 @@ __host__ __device__ inline int link_lds_floats(const WideLayout& L, bool w_last,
 //                        x_T = (x_T - t) exp(-s), ActNorm^-1 after its last half. The reference's two_way inverse
 //                        (cnf.py:198-213) runs nn_a then nn_b, both on the current state -- not the true inverse; the
 //                        processing order of the host loop reproduces exactly that.   (cnf.py:337-339, 353-354)
+//                        With a.ldj (one-way stacks only): the forward's log|det J| at the returned y as a running
+//                        a.ldj[row] across the link launches -- the tail's tanh(s) IS the forward's s there (the
+//                        identity half passes through), plus the ActNorm constant pk_ldc[k] once per real block;
+//                        block 0's tail also writes log_prob = -0.5 |z|^2 + ldj - D/2 log 2pi (a.logp, z = a.xin).
 // DD > 0: the sample dimension D as a compile-time constant (every loop over D and the per-side widths fully
 // unrolled); DD = 0: runtime D (any D <= 32).
-template <bool INV, int DD, int TS, int HS>
+// LDJ (inverse of a one-way stack with a.ldj set): its own instantiation, so the plain inverse keeps its code.
+template <bool INV, int DD, int TS, int HS, bool LDJ = false>
 __global__ __launch_bounds__(WWG) void k_wlink(const WideLayout L, const LinkArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, ln = tid & 31, r = tid >> 5;
@@ -1512,6 +1518,7 @@ __global__ __launch_bounds__(WWG) void k_wlink(const WideLayout L, const LinkArg
     offs = a.rng[1];
   }
   float xi = 0.f;                                   // element ln of the sample's D-vector
+  float s_ldj = 0.f;                                // LDJ: the tail's tanh(s) of a transformed lane
   // ------------------------------------------------------------ tail of virtual block vt
   if (vt >= 0 && !dots) {                          // the partials of the chain's last GEMM, summed in column order
     if (ln < O2) {
@@ -1570,7 +1577,10 @@ __global__ __launch_bounds__(WWG) void k_wlink(const WideLayout L, const LinkArg
           if (a.S) a.S[row * L.SP + jt] = sj;
         }
       } else {
-        if (tl) xi = (xi - Os[jt]) * exp_fast(-tanh_bf(Os[nout_t + jt]));   // (x_T - t) exp(-s) (cnf.py:201, 208)
+        if (tl) {
+          sj = tanh_bf(Os[nout_t + jt]);
+          xi = (xi - Os[jt]) * exp_fast(-sj);                     // (x_T - t) exp(-s) (cnf.py:201, 208)
+        }
         if (t_last && L.an && kt < L.nb - 1) xi = (xi - bct) / sct;            // ActNorm inverse (cnf.py:354)
       }
     }
@@ -1598,8 +1608,9 @@ __global__ __launch_bounds__(WWG) void k_wlink(const WideLayout L, const LinkArg
           if (a.nllp) a.nllp[row] = 0.5f * zz - lj;               // per-sample inn_nll_loss (utils.py:49-53)
         }
       }
-    } else if (t_last && kt == 0 && lv) {
-      a.z[row * D + ln] = xi;
+    } else {
+      if (LDJ) s_ldj = sj;
+      if (t_last && kt == 0 && lv) a.z[row * D + ln] = xi;
     }
   } else {
     xi = xpre;
@@ -1673,6 +1684,18 @@ __global__ __launch_bounds__(WWG) void k_wlink(const WideLayout L, const LinkArg
       for (int t = 0; t < MQ; ++t)
         if (ln + 32 * t < nq) chunk(ln + 32 * t, pch[t], bch[t]);
       for (int q = ln + 32 * MQ; q < nq; q += 32) chunk(q, ld4(Pr + 4 * q), ld4(b0 + 4 * q));
+    }
+  }
+  if (LDJ && vt >= 0) {     // the log|det dz/dy| at the returned y; last, when the head's registers are free
+    const float ssum = half_sum(s_ldj);
+    const bool fin = kt == 0 && a.logp;
+    const float zi = (fin && lv) ? a.xin[row * D + ln] : 0.f;
+    const float zz = half_sum(zi * zi);
+    if (valid && ln == 0) {
+      float lj = (kt == L.nb - 1 ? 0.f : a.ldj[row]) + ssum;      // the first tail launch starts the sum
+      if (L.an && kt < L.nb - 1) lj += a.pk[L.pk_ldc + kt];       // ActNorm log|det J| (cnf.py:349)
+      a.ldj[row] = lj;
+      if (fin) a.logp[row] = -(0.5f * zz - lj) - 0.5f * (float)D * 1.8378770664093454836f;
     }
   }
   LINK_STAMP(6);
@@ -2390,7 +2413,8 @@ WideWs carve(const WideLayout& L, long long B, bool train, float* base) {
 // launch is free, so every launch maps onto (0,0) [one-way], (0,1) or (1,0) [two_way].
 template <bool INV, int DD>
 void link_dispatch(int ts, int hs, dim3 grid, size_t lds, hipStream_t st, const WideLayout& L, const LinkArgs& a) {
-  if (L.S == 1) hipLaunchKernelGGL((k_wlink<INV, DD, 0, 0>), grid, dim3(WWG), lds, st, L, a);
+  if (INV && a.ldj) hipLaunchKernelGGL((k_wlink<INV, DD, 0, 0, INV>), grid, dim3(WWG), lds, st, L, a);   // S == 1
+  else if (L.S == 1) hipLaunchKernelGGL((k_wlink<INV, DD, 0, 0>), grid, dim3(WWG), lds, st, L, a);
   else if (ts == 0 && hs == 1) hipLaunchKernelGGL((k_wlink<INV, DD, 0, 1>), grid, dim3(WWG), lds, st, L, a);
   else hipLaunchKernelGGL((k_wlink<INV, DD, 1, 0>), grid, dim3(WWG), lds, st, L, a);
 }
@@ -2447,7 +2471,8 @@ void ensure_lds_attrs() {
       (const void*)k_wlink<false, 19, 0, 0>, (const void*)k_wlink<false, 19, 0, 1>,
       (const void*)k_wlink<false, 19, 1, 0>, (const void*)k_wlink_bwd<0, 0, 0>, (const void*)k_wlink_bwd<0, 0, 1>,
       (const void*)k_wlink_bwd<0, 1, 0>,    (const void*)k_wlink_bwd<19, 0, 0>, (const void*)k_wlink_bwd<19, 0, 1>,
-      (const void*)k_wlink_bwd<19, 1, 0>};
+      (const void*)k_wlink_bwd<19, 1, 0>,   (const void*)k_wlink<true, 0, 0, 0, true>,
+      (const void*)k_wlink<true, 19, 0, 0, true>};
   for (const void* f : fns) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   lds_attr_done = true;
 }
@@ -2819,7 +2844,7 @@ long long inverse_scratch_floats(const WideLayout& L, long long hrows, long long
 
 int wide_inverse(const WideLayout& L, const float* prm, const float* pk, const float* z, const float* h, long long hrows,
                  const int64_t* cidx, long long n, float* y, bool training, const uint64_t* rng, float* scratch,
-                 hipStream_t st) {
+                 hipStream_t st, float* ldj = nullptr, float* logp = nullptr) {
   if (n == 0) return BCNF_OK;
   ensure_lds_attrs();
   const bool drop = training && L.p > 0.f && rng;
@@ -2859,6 +2884,8 @@ int wide_inverse(const WideLayout& L, const float* prm, const float* pk, const f
     a.cidx = cidx;
     a.A0 = Ap(0);
     a.rng = drop ? rng : nullptr;
+    a.ldj = ldj;                                     // nullptr: the plain inverse
+    a.logp = logp;
     WCHK(link_launch(L, a, true, st));
   }
   return BCNF_OK;
@@ -3078,6 +3105,23 @@ int bcnf_wide_inverse(const BcnfStackDesc* desc, const float* params, const void
   if (!cond_index && h_rows != n_rows) return BCNF_ERR_ARG;
   return wide_inverse(L, params, (const float*)packed, z, h, h_rows, cond_index, n_rows, y, training != 0, rng_state,
                       (float*)scratch, (hipStream_t)stream);
+}
+
+int bcnf_wide_inverse_logdet(const BcnfStackDesc* desc, const float* params, const void* packed, const float* z,
+                             const float* h, int64_t h_rows, const int64_t* cond_index, int64_t n_rows, float* y,
+                             float* ldj, float* log_prob, void* scratch, void* stream) {
+  if (!desc) return BCNF_ERR_ARG;
+  if (desc->two_way) return BCNF_ERR_UNSUPPORTED;   // the reference's two_way inverse is not its forward's inverse
+  if (!y || !ldj) return BCNF_ERR_ARG;
+  WideLayout L;
+  WCHK(wide_layout(desc, &L));
+  if (n_rows < 0 || h_rows < 0) return BCNF_ERR_ARG;
+  if (n_rows == 0) return BCNF_OK;
+  if (!params || !packed || !z || !h || !scratch || !aligned16(scratch) || (L.Cp == L.C && !aligned16(h)))
+    return BCNF_ERR_ARG;
+  if (!cond_index && h_rows != n_rows) return BCNF_ERR_ARG;
+  return wide_inverse(L, params, (const float*)packed, z, h, h_rows, cond_index, n_rows, y, false, nullptr,
+                      (float*)scratch, (hipStream_t)stream, ldj, log_prob);
 }
 
 #ifdef BCNF_PHASE_STAMPS

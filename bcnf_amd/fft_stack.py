@@ -143,11 +143,13 @@ class FFTWideStack(WideStack):
         dy, dh, dparams = super().launch_nll_backward(h, z, dvals, training, saved, want_dy, want_dh, **kw)
         return dy, dh, self.unfold_grad(dparams)
 
-    def launch_inverse(self, z, h, cond_index=None, training: bool = False):
+    def launch_inverse(self, z, h, cond_index=None, training: bool = False, want_ldj: bool = False):
+        if want_ldj:
+            self._check_ldj(training)
         self._check_inputs(z, h, "inverse")
         if not self._pack_frozen:
             self.refresh()
-        return super().launch_inverse(z, h, cond_index, training)
+        return super().launch_inverse(z, h, cond_index, training, want_ldj)
 
     def reuse_pack(self):
         self.refresh()

@@ -16,6 +16,7 @@ per-layer `.grad` tensors as views of that flat gradient.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from dataclasses import dataclass
 
@@ -574,7 +575,21 @@ class FusedStack:
                 ctypes.c_int32(int(training)), N.ptr(rng), N.ptr(ws), ctypes.c_int32(0), N.ptr(vals), None, stream)
         return self._event_times(calls, iters)
 
-    def launch_inverse(self, z, h, cond_index=None, training: bool = False):
+    def _check_ldj(self, training: bool):
+        """The density of a draw exists only where the inverse is the forward's inverse and deterministic."""
+        if self.cfg.two_way:
+            raise ValueError("bcnf_amd: no log-density for two_way stacks: the reference's two_way inverse "
+                             "(cnf.py:198-213) is not the inverse of its forward")
+        if training and self.cfg.dropout > 0.0:
+            raise ValueError("bcnf_amd: no log-density for a training-mode inverse with dropout > 0 (the draw is not "
+                             "deterministic); call model.eval() first")
+
+    def launch_inverse(self, z, h, cond_index=None, training: bool = False, want_ldj: bool = False):
+        """y = inverse(z | h). want_ldj=True (eval, one-way): (y, ldj, log_prob) with ldj = log|det dz/dy| at the
+        returned y (what launch_forward(y, h) gives) and log_prob = -0.5 |z|^2 + ldj - D/2 log 2pi, from the same
+        launch; y is bit-identical to the plain call."""
+        if want_ldj:
+            self._check_ldj(training)
         self._check_inputs(z, h, "inverse")
         n = z.shape[0]
         if cond_index is None and h.shape[0] != n:
@@ -587,6 +602,20 @@ class FusedStack:
         hr = h.shape[0]
         sb = N.query_i64(N.lib().bcnf_inverse_scratch_bytes, self._pdesc, ctypes.c_int64(hr))
         scratch = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=z.device)
+        if want_ldj:
+            ldj = torch.empty(n, dtype=torch.float32, device=z.device)
+            logp = torch.empty(n, dtype=torch.float32, device=z.device)
+            rc = N.lib().bcnf_stack_inverse_logdet(self._pdesc, N.ptr(self.packed()), N.ptr(z), N.ptr(h),
+                                                   ctypes.c_int64(hr), N.ptr(cond_index), ctypes.c_int64(n), N.ptr(y),
+                                                   N.ptr(ldj), N.ptr(logp), N.ptr(scratch), N.stream_handle(z.device))
+            if rc == N.ERR_UNSUPPORTED:
+                # a layout outside the matrix-core inverse: the plain inverse, then the forward kernels at y
+                y = self.launch_inverse(z, h, cond_index, training)
+                hh = h if cond_index is None else h.index_select(0, cond_index)
+                _, ldj, _, _ = self.launch_forward(y, hh.contiguous(), False, save=False)
+                return y, ldj, log_prob_of_latent(z, ldj)
+            N.check(rc, "bcnf_stack_inverse_logdet")
+            return y, ldj, logp
         rc = N.lib().bcnf_stack_inverse(self._pdesc, N.ptr(self.packed()), N.ptr(z), N.ptr(h), ctypes.c_int64(hr),
                                         N.ptr(cond_index), ctypes.c_int64(n), N.ptr(y), ctypes.c_int32(int(training)),
                                         N.ptr(rng), N.ptr(scratch), N.stream_handle(z.device))
@@ -810,13 +839,21 @@ def stack_nll_fold(stack: FusedStack, y, x, wf, bf, training: bool, defer: bool 
     return stack.launch_fold_nll_forward(y, x, wf, bf, training, gather=gather)[2]
 
 
+def log_prob_of_latent(z, ldj):
+    """-0.5 |z|^2 + ldj - D/2 log 2pi (utils.log_prob_from_latent) for the composed fall-back."""
+    return -0.5 * z.pow(2).sum(dim=-1) + ldj - 0.5 * z.shape[-1] * math.log(2.0 * math.pi)
+
+
 class _StackInverse(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, z, h, stack: FusedStack, cond_index, training: bool):
-        return stack.launch_inverse(z, h, cond_index, training)
+    def forward(ctx, z, h, stack: FusedStack, cond_index, training: bool, want_ldj: bool = False):
+        out = stack.launch_inverse(z, h, cond_index, training, want_ldj)
+        if want_ldj:
+            ctx.mark_non_differentiable(*out[1:])
+        return out
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, *unused):
         raise NotImplementedError("bcnf_amd: CondRealNVP_v2.inverse is not differentiable (sampling path); "
                                   "run it under torch.no_grad().")
 
@@ -845,11 +882,13 @@ def stack_forward(stack: FusedStack, y, h, training: bool, flat=None):
     return z, ldj
 
 
-def stack_inverse(stack: FusedStack, z, h, cond_index=None, training: bool = False, flat=None):
+def stack_inverse(stack: FusedStack, z, h, cond_index=None, training: bool = False, flat=None,
+                  want_ldj: bool = False):
+    """want_ldj=True: (y, ldj, log_prob) -- see FusedStack.launch_inverse."""
     z = z.contiguous()
     h = h.contiguous()
     if flat is not None:
         _set_standalone_params(stack, flat, z.device)
     if torch.is_grad_enabled() and (z.requires_grad or h.requires_grad):
-        return _StackInverse.apply(z, h, stack, cond_index, training)
-    return stack.launch_inverse(z, h, cond_index, training)
+        return _StackInverse.apply(z, h, stack, cond_index, training, want_ldj)
+    return stack.launch_inverse(z, h, cond_index, training, want_ldj)

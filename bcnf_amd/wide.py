@@ -324,7 +324,9 @@ class WideStack(FusedStack):
             out[name] = e0.elapsed_time(e1) * 1e3 / iters
         return out
 
-    def launch_inverse(self, z, h, cond_index=None, training: bool = False):
+    def launch_inverse(self, z, h, cond_index=None, training: bool = False, want_ldj: bool = False):
+        if want_ldj:
+            self._check_ldj(training)
         self._check_inputs(z, h, "inverse")
         n = z.shape[0]
         if cond_index is None and h.shape[0] != n:
@@ -337,6 +339,15 @@ class WideStack(FusedStack):
         hr = h.shape[0]
         sb = N.query_i64(N.lib().bcnf_wide_inverse_scratch_bytes, self._pdesc, ctypes.c_int64(hr), ctypes.c_int64(n))
         scratch = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=z.device)
+        if want_ldj:
+            ldj = torch.empty(n, dtype=torch.float32, device=z.device)
+            logp = torch.empty(n, dtype=torch.float32, device=z.device)
+            rc = N.lib().bcnf_wide_inverse_logdet(self._pdesc, N.ptr(self.flat), N.ptr(self.packed()), N.ptr(z),
+                                                  N.ptr(h), ctypes.c_int64(hr), N.ptr(cond_index), ctypes.c_int64(n),
+                                                  N.ptr(y), N.ptr(ldj), N.ptr(logp), N.ptr(scratch),
+                                                  N.stream_handle(z.device))
+            N.check(rc, "bcnf_wide_inverse_logdet")
+            return y, ldj, logp
         rc = N.lib().bcnf_wide_inverse(self._pdesc, N.ptr(self.flat), N.ptr(self.packed()), N.ptr(z), N.ptr(h),
                                        ctypes.c_int64(hr), N.ptr(cond_index), ctypes.c_int64(n), N.ptr(y),
                                        ctypes.c_int32(int(training)), N.ptr(rng), N.ptr(scratch),

@@ -20,6 +20,7 @@
  *                           cnf.py:353-354, coupling inverse cnf.py:198-213, orthonormal inverse
  *                           cnf.py:337-339); with cond_index it also serves _sample's tiled
  *                           conditions (cnf.py:577-582) without materialising the tiled features
+ *   bcnf_stack_inverse_logdet <- the same loop plus the forward's log|det J| (cnf.py:477,488) at the returned y
  *   bcnf_pack_params     <- (no reference counterpart) re-lays the nn.Module parameters into the
  *                           kernels' LDS-record layout; call after every parameter update
  *   bcnf_nll_forward     <- Trainer._train_batch forward + loss, trainer.py:260-266: the stack forward
@@ -225,6 +226,19 @@ int bcnf_stack_inverse(const BcnfStackDesc* desc, const void* packed, const floa
                        int64_t h_rows, const int64_t* cond_index, int64_t n_rows, float* y, int32_t training,
                        const uint64_t* rng_state, void* scratch, void* stream);
 
+/* Inverse (eval) that also returns the density of what it returns: ldj (N) = log|det dz/dy| at the returned y, the
+ * value bcnf_stack_forward(y, h) writes to its ldj (same sign), and log_prob (N, nullable) = -0.5 |z|^2 + ldj -
+ * D/2 log 2pi with z the rows as passed (utils.py:49-53 at the draw). A one-way coupling's inverse passes the identity
+ * half through unchanged (cnf.py:198-213), so the s = tanh(s') it forms at block k is the forward's s at y: the
+ * kernel keeps their running sum (one add per coupling output) and adds the packed ActNorm constant; no second pass
+ * over the n_rows rows. Eval only (no dropout: the draw is deterministic). y is bit-identical to bcnf_stack_inverse's.
+ * two_way descriptors return BCNF_ERR_UNSUPPORTED (the reference's two_way inverse is not its forward's inverse, so
+ * there is no density), as does a layout outside the matrix-core inverse. Arguments are validated before any HIP
+ * call; NULL y / ldj is BCNF_ERR_ARG. Scratch as bcnf_stack_inverse. A row's result does not depend on its position. */
+int bcnf_stack_inverse_logdet(const BcnfStackDesc* desc, const void* packed, const float* z, const float* h,
+                              int64_t h_rows, const int64_t* cond_index, int64_t n_rows, float* y, float* ldj,
+                              float* log_prob /* nullable */, void* scratch, void* stream);
+
 /* ---- NLL training pass (forward + inn_nll_loss + backward without any host round trip) ---------
  * bcnf_nll_forward = bcnf_stack_forward (workspace required, save on) plus per-workgroup partials of
  *   nll = mean_b(0.5 |z_b|^2 - ldj_b)  (utils.py:40-46). With finalize != 0 a one-workgroup launch then
@@ -429,6 +443,11 @@ int bcnf_wide_proj_rows(const BcnfStackDesc* desc, int64_t* rows);
 int bcnf_wide_inverse(const BcnfStackDesc* desc, const float* params, const void* packed, const float* z,
                       const float* h, int64_t h_rows, const int64_t* cond_index, int64_t n_rows, float* y,
                       int32_t training, const uint64_t* rng_state, void* scratch, void* stream);
+/* As bcnf_stack_inverse_logdet for the wide family (one-way stacks; two_way: BCNF_ERR_UNSUPPORTED): the link kernels
+ * carry ldj[row] across their launches and add each block's ActNorm constant once; the GEMM chain is unchanged. */
+int bcnf_wide_inverse_logdet(const BcnfStackDesc* desc, const float* params, const void* packed, const float* z,
+                             const float* h, int64_t h_rows, const int64_t* cond_index, int64_t n_rows, float* y,
+                             float* ldj, float* log_prob /* nullable */, void* scratch, void* stream);
 /* ---- Hybrid training loss: prediction head + MSE (cnf.py: prediction_head = nn.Linear(C, D); trainer.py:261-269
  * with hybrid_weight w > 0: loss = (nll + w * MSE(prediction_head(h), y)) / (1 + w)) ---------------------------------
  * x (B x K, rows ldx >= K floats apart; columns K .. ldx are never read into a result), W (D x K), bias (D, nullable),
