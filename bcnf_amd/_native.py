@@ -269,7 +269,32 @@ def i64_array(values):
     return arr
 
 
+def call_raw(name: str, *args) -> int:
+    """lib().<name>(*args) -> what it returns (its status; a size for the few entry points that return one). Tensors
+    go as their data_ptr(), None as NULL, a ctypes.Structure by reference; everything else (Python scalars, byref
+    objects, ctypes arrays, c_void_p stream handles) is converted by the argtypes `_bind` declares."""
+    return getattr(lib(), name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else
+                                  ctypes.byref(a) if isinstance(a, ctypes.Structure) else a for a in args])
+
+
+def call(name: str, *args) -> None:
+    """call_raw that raises on a non-OK status (see check)."""
+    check(call_raw(name, *args), name)
+
+
+def query_status(name: str, *args, outs: int = 1):
+    """(status, the int64 values the entry point writes through its `outs` trailing out-pointers)."""
+    out = [ctypes.c_int64(0) for _ in range(outs)]
+    rc = call_raw(name, *args, *[ctypes.byref(o) for o in out])
+    return rc, [int(o.value) for o in out]
+
+
 def query_i64(fn, *args) -> int:
+    """The int64 a size query writes through its trailing out-pointer; fn = an entry point's name or the function."""
+    if isinstance(fn, str):
+        rc, (value,) = query_status(fn, *args)
+        check(rc, fn)
+        return value
     out = ctypes.c_int64(0)
     check(fn(*args, ctypes.byref(out)), fn.__name__)
     return int(out.value)

@@ -28,8 +28,7 @@ def rank_count_(counts: torch.Tensor, y_hat: torch.Tensor, y: torch.Tensor) -> t
             raise RuntimeError("bcnf_amd rank counting runs on the GPU only")
     y_hat = y_hat.to(torch.float32).contiguous()
     y = y.to(torch.float32).contiguous()
-    N.check(N.lib().bcnf_rank_count(N.ptr(y_hat), N.ptr(y), y_hat.shape[0], y.shape[0], y.shape[1], N.ptr(counts),
-                                    N.stream_handle(y.device)), "bcnf_rank_count")
+    N.call("bcnf_rank_count", y_hat, y, y_hat.shape[0], y.shape[0], y.shape[1], counts, N.stream_handle(y.device))
     return counts
 
 

@@ -28,7 +28,7 @@ from bcnf_amd.factories import FeatureNetworkFactory, LayerFactory
 from bcnf_amd.feature_network import (ConcatenateCondition, FeatureNetwork, FeatureNetworkStack,
                                       FullyConnectedFeatureNetwork, HIPLinear, LSTMFeatureNetwork, bind_rng_owner)
 from bcnf_amd.fft_stack import FFTWideStack
-from bcnf_amd.fused import (FusedStack, StackConfig, stack_forward, stack_hybrid, stack_inverse, stack_nll,
+from bcnf_amd.fused import (FusedStack, StackBase, StackConfig, stack_forward, stack_hybrid, stack_inverse, stack_nll,
                             stack_nll_fold)
 from bcnf_amd.layers import AnyGLU, LinearFFTEnriched
 from bcnf_amd.wide import WideStack, make_stack, stack_nll_wide_fold
@@ -192,7 +192,7 @@ class ConditionalAffineCouplingLayer(ConditionalInvertibleLayer):
     def canonical_params(self) -> list[nn.Parameter]:
         return self.nn_a.canonical_params()
 
-    def _standalone(self) -> tuple[FusedStack, torch.Tensor]:
+    def _standalone(self) -> tuple[StackBase, torch.Tensor]:
         _check_fused_family(*self._fam, self.two_way)
         cfg = StackConfig(self.input_size, tuple(self.nested_sizes), 1, self.n_conditions, self.dropout, False,
                           self.two_way)
@@ -420,7 +420,7 @@ class CondRealNVP_v2(ConditionalInvertibleLayer):
         return out
 
     @property
-    def fused(self) -> FusedStack:
+    def fused(self) -> StackBase:
         return self._fused
 
     def flat_parameters(self) -> list[nn.Parameter]:
@@ -796,7 +796,7 @@ class _LayerwiseStack:
         return y, ldj
 
     def inverse(self, z: torch.Tensor, h: torch.Tensor, want_ldj: bool = False):
-        """want_ldj=True (one-way, deterministic): (y, ldj, log_prob) as FusedStack.launch_inverse -- the same running
+        """want_ldj=True (one-way, deterministic): (y, ldj, log_prob) as StackBase.launch_inverse -- the same running
         sum of the couplings' log-scales and the ActNorm constants, with torch ops."""
         self._check(z)
         z_in = z

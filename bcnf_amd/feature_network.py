@@ -29,8 +29,7 @@ class _LinearFn(torch.autograd.Function):
         rows, k = x.shape
         n = weight.shape[0]
         y = torch.empty((rows, n), dtype=torch.float32, device=x.device)
-        N.check(N.lib().bcnf_linear_forward(N.ptr(x), N.ptr(weight), N.ptr(bias), rows, k, n, N.ptr(y),
-                                            N.stream_handle(x.device)), "bcnf_linear_forward")
+        N.call("bcnf_linear_forward", x, weight, bias, rows, k, n, y, N.stream_handle(x.device))
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return y
@@ -48,11 +47,9 @@ class _LinearFn(torch.autograd.Function):
         db = torch.empty(n, dtype=torch.float32, device=x.device) if (need_b and ctx.has_bias) else None
         work = None
         if dw is not None:
-            wb = int(N.lib().bcnf_linear_work_bytes(rows, k, n))
+            wb = N.call_raw("bcnf_linear_work_bytes", rows, k, n)
             work = torch.empty(max(wb // 4, 1), dtype=torch.float32, device=x.device)
-        N.check(N.lib().bcnf_linear_backward(N.ptr(x), N.ptr(weight), N.ptr(dy), rows, k, n, N.ptr(dx), N.ptr(dw),
-                                             N.ptr(db), N.ptr(work), N.stream_handle(x.device)),
-                "bcnf_linear_backward")
+        N.call("bcnf_linear_backward", x, weight, dy, rows, k, n, dx, dw, db, work, N.stream_handle(x.device))
         return dx, (dw if need_w else None), db
 
 
@@ -68,9 +65,8 @@ class _LinearGeluFn(torch.autograd.Function):
         n = weight.shape[0]
         a = torch.empty((rows, n), dtype=torch.float32, device=x.device)
         g = torch.empty_like(a) if need_g else None
-        N.check(N.lib().bcnf_linear_gelu_forward(N.ptr(x), N.ptr(weight), N.ptr(bias), rows, k, n, float(p),
-                                                 N.ptr(rng), int(salt), N.ptr(a), N.ptr(g),
-                                                 N.stream_handle(x.device)), "bcnf_linear_gelu_forward")
+        N.call("bcnf_linear_gelu_forward", x, weight, bias, rows, k, n, float(p), rng, int(salt), a, g,
+               N.stream_handle(x.device))
         ctx.save_for_backward(x, weight, g)
         ctx.has_bias = bias is not None
         return a
@@ -90,11 +86,9 @@ class _LinearGeluFn(torch.autograd.Function):
         db = torch.empty(n, dtype=torch.float32, device=x.device) if (need_b and ctx.has_bias) else None
         work = None
         if dw is not None:
-            wb = int(N.lib().bcnf_linear_work_bytes(rows, k, n))
+            wb = N.call_raw("bcnf_linear_work_bytes", rows, k, n)
             work = torch.empty(max(wb // 4, 1), dtype=torch.float32, device=x.device)
-        N.check(N.lib().bcnf_linear_gelu_backward(N.ptr(x), N.ptr(weight), N.ptr(da), N.ptr(g), rows, k, n, N.ptr(dx),
-                                                  N.ptr(dw), N.ptr(db), N.ptr(work), N.stream_handle(x.device)),
-                "bcnf_linear_gelu_backward")
+        N.call("bcnf_linear_gelu_backward", x, weight, da, g, rows, k, n, dx, dw, db, work, N.stream_handle(x.device))
         return dx, (dw if need_w else None), db, None, None, None, None
 
 
@@ -168,7 +162,7 @@ class FullyConnectedFeatureNetwork(FeatureNetwork):
     # dropout and `model.fused.set_seed` / TrainStep's snapshot cover both; else this module's own state.
     # Advancing: the owner's coupling launch bumps the shared offset once per training step when the coupling itself
     # drops out (and a feature draw that no coupling launch followed -- this network run on its own -- is advanced
-    # at the next draw, FusedStack.feature_rng_state); otherwise (coupling dropout 0, the owner in eval mode or
+    # at the next draw, StackBase.feature_rng_state); otherwise (coupling dropout 0, the owner in eval mode or
     # elsewhere, no owner) run() bumps it after the network's last fused dropout layer -- a device-side add,
     # replay-safe in HIP graphs -- so every training step draws fresh feature masks.
     _own_rng = None
@@ -178,7 +172,7 @@ class FullyConnectedFeatureNetwork(FeatureNetwork):
 
     def _rng(self, device, draw: bool = True) -> tuple[torch.Tensor, bool]:
         """(device (seed, offset) state, whether the owner's coupling launch advances it this step); draw: the
-        caller draws from it now (marks the draw on the owner's stack, see FusedStack.feature_rng_state)."""
+        caller draws from it now (marks the draw on the owner's stack, see StackBase.feature_rng_state)."""
         ref = _RNG_OWNERS.get(self)
         owner = ref() if ref is not None else None
         fused = owner.__dict__.get("_fused") if owner is not None else None

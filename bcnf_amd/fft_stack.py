@@ -27,8 +27,7 @@ def _linear(x, w):
     n = w.shape[0]
     y = torch.empty((rows, n), dtype=torch.float32, device=x.device)
     if rows and n:
-        N.check(N.lib().bcnf_linear_forward(N.ptr(x), N.ptr(w), None, rows, k, n, N.ptr(y), N.stream_handle(x.device)),
-                "bcnf_linear_forward")
+        N.call("bcnf_linear_forward", x, w, None, rows, k, n, y, N.stream_handle(x.device))
     return y
 
 
@@ -41,40 +40,17 @@ class FFTWideStack(WideStack):
         super().__init__(cfg, trainable, frozen, bind)
 
     def flatten(self):
-        params = self.trainable
-        dev = params[0].device
-        ncan = sum(p.numel() for p in params)
-        canon = torch.empty(ncan, dtype=torch.float32, device=dev)
-        maps, off, eoff = [], 0, 0
-        with torch.no_grad():
-            for p, n in zip(params, self.fft_n):
-                k = p.numel()
-                canon[off:off + k].copy_(p.detach().reshape(-1))
-                p.data = canon[off:off + k].view(p.shape)
-                ek = p.shape[0] * n if n is not None else k
-                maps.append((off, tuple(p.shape), eoff, n))
-                off += k
-                eoff += ek
-        nq = sum(q.numel() for q in self.frozen)
-        qflat = torch.empty(max(nq, 1), dtype=torch.float32, device=dev)
-        qo = 0
-        with torch.no_grad():
-            for q in self.frozen:
-                k = q.numel()
-                qflat[qo:qo + k].copy_(q.detach().reshape(-1))
-                q.data = qflat[qo:qo + k].view(q.shape)
-                qo += k
-        self.canon = canon
+        super().flatten()                 # flat_param and the per-layer views are over the canonical buffer
+        self.canon = self.flat
+        dev = self.canon.device
+        maps, eoff = [], 0
+        for p, (off, k), n in zip(self.trainable, self._offsets, self.fft_n):
+            maps.append((off, tuple(p.shape), eoff, n))
+            eoff += p.shape[0] * n if n is not None else k
         self.flat = torch.empty(eoff, dtype=torch.float32, device=dev)    # what the kernels read (Linear layout)
-        self.qflat = qflat
-        self.flat_param = torch.nn.Parameter(canon, requires_grad=True)
-        self.flat_param.register_post_accumulate_grad_hook(self._on_flat_grad)
-        self._offsets = [(o, int(torch.Size(s).numel())) for o, s, _, _ in maps]
         self._maps = maps
         self._F = {n: rfft_matrix(n, device=dev) for n in set(x for x in self.fft_n if x is not None)}
         self._Ft = {n: f.t().contiguous() for n, f in self._F.items()}
-        self._packed = None
-        self._rng_state = None
 
     # ------------------------------------------------------------------ canonical <-> effective
     def refresh(self):
@@ -154,3 +130,8 @@ class FFTWideStack(WideStack):
     def reuse_pack(self):
         self.refresh()
         return super().reuse_pack()
+
+    def time_kernels(self, y, h, **kw):
+        self._check_inputs(y, h, "forward")
+        self.refresh()
+        return super().time_kernels(y, h, **kw)

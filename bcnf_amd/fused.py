@@ -40,8 +40,10 @@ class StackConfig:
                            self.act_norm, self.two_way)
 
 
-class FusedStack:
-    """Owns the flat parameter buffers of one coupling stack and drives the HIP kernels."""
+class StackBase:
+    """What the kernel families share: the flat parameter buffers of one coupling stack, the pack policy, the dropout
+    RNG state, TrainStep's hooks, the inverse and the timing loop. A family (FusedStack here, WideStack in wide.py)
+    adds `supported`, `counts`, its packed-bytes query, `_pack_into`, the inverse's native calls and its launches."""
 
     def __init__(self, cfg: StackConfig, trainable: list, frozen: list, bind: bool = True):
         self.cfg = cfg
@@ -55,7 +57,6 @@ class FusedStack:
         self._pack_frozen = False
         self._rng_state = None
         self.seed = None
-        self.timers = None       # dict -> per-kernel HIP-event pairs (bench.py kernel timing phase)
         self.guard = None        # device int32[BCNF_GUARD_WORDS] divergence guard of a TrainStep, or None
         if bind:
             self.flatten()
@@ -65,50 +66,34 @@ class FusedStack:
             self.flat_param = None
 
     # ------------------------------------------------------------------ layout
-    @property
-    def supported(self) -> bool:
-        return bool(N.lib().bcnf_stack_supported(self._pdesc))
-
-    def counts(self):
-        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
-        N.check(N.lib().bcnf_param_count(self._pdesc, ctypes.byref(a), ctypes.byref(b)), "bcnf_param_count")
-        return int(a.value), int(b.value)
+    @staticmethod
+    def _gather_views(tensors, dev, min_numel: int = 0):
+        """Copy the tensors into one fp32 buffer on `dev` and rebind every `.data` to its view of that buffer."""
+        flat = torch.empty(max(sum(t.numel() for t in tensors), min_numel), dtype=torch.float32, device=dev)
+        off = 0
+        with torch.no_grad():
+            for t in tensors:
+                k = t.numel()
+                flat[off:off + k].copy_(t.detach().reshape(-1))
+                t.data = flat[off:off + k].view(t.shape)
+                off += k
+        return flat
 
     def flatten(self):
         """(Re)build the flat buffers on the parameters' current device and rebind every Parameter
         to a view of them. Called at construction and after every Module._apply (to(), cuda(), ...)."""
-        params = self.trainable
-        dev = params[0].device
-        n = sum(p.numel() for p in params)
-        flat = torch.empty(n, dtype=torch.float32, device=dev)
-        off = 0
-        with torch.no_grad():
-            for p in params:
-                k = p.numel()
-                flat[off:off + k].copy_(p.detach().reshape(-1))
-                p.data = flat[off:off + k].view(p.shape)
-                off += k
-        nq = sum(q.numel() for q in self.frozen)
-        qflat = torch.empty(max(nq, 1), dtype=torch.float32, device=dev)
-        off = 0
-        with torch.no_grad():
-            for q in self.frozen:
-                k = q.numel()
-                qflat[off:off + k].copy_(q.detach().reshape(-1))
-                q.data = qflat[off:off + k].view(q.shape)
-                off += k
-        self.flat = flat
-        self.qflat = qflat
-        self.flat_param = torch.nn.Parameter(flat, requires_grad=True)
+        dev = self.trainable[0].device
+        self.flat = self._gather_views(self.trainable, dev)
+        self.qflat = self._gather_views(self.frozen, dev, 1)
+        self.flat_param = torch.nn.Parameter(self.flat, requires_grad=True)
         self.flat_param.register_post_accumulate_grad_hook(self._on_flat_grad)
         self._offsets = []
         off = 0
-        for p in params:
+        for p in self.trainable:
             self._offsets.append((off, p.numel()))
             off += p.numel()
         self._packed = None
         self._rng_state = None
-        self._raw_tables = {}
 
     def _on_flat_grad(self, fp):
         if self.grad_mode != "per_param" or fp.grad is None:
@@ -131,6 +116,11 @@ class FusedStack:
             raise ValueError(f"bcnf_amd {what}: expected features (N, {cfg.n_conditions}), got {tuple(h.shape)}")
         self._check_device(x, h)
 
+    def _check_forward(self, y, h):
+        self._check_inputs(y, h, "forward")
+        if h.shape[0] != y.shape[0]:
+            raise ValueError(f"bcnf_amd forward: {y.shape[0]} samples but {h.shape[0]} feature rows")
+
     def _check_device(self, *tensors):
         for t in tensors:
             if t is None:
@@ -143,27 +133,24 @@ class FusedStack:
         if self.flat is None or self.flat.device.type != "cuda":
             raise RuntimeError("bcnf_amd: model parameters are not on the GPU; call model.to('cuda') first.")
 
+    # ------------------------------------------------------------------ pack policy
     def packed(self, fresh: bool = False):
-        """Packed LDS-record buffer. Re-packed on every call unless inside `reuse_pack()` (parameters
-        change in place after each optimizer step; `.data`-rebound views do not share one reliable
+        """The family's packed parameter buffer (`_pack_into`). Re-packed on every call unless inside `reuse_pack()`
+        (parameters change in place after each optimizer step; `.data`-rebound views do not share one reliable
         version counter, so no staleness heuristics). Under HIP-graph capture the pack is a graph node."""
         if fresh and not self._pack_frozen:
             # private copy that a later forward cannot overwrite before this one's backward runs
-            nbytes = N.query_i64(N.lib().bcnf_packed_bytes, self._pdesc)
-            out = torch.empty(nbytes // 4, dtype=torch.float32, device=self.flat.device)
+            out = self._empty_pack()
             self._pack_into(out)
             return out
         if self._packed is None:
-            nbytes = N.query_i64(N.lib().bcnf_packed_bytes, self._pdesc)
-            self._packed = torch.empty(nbytes // 4, dtype=torch.float32, device=self.flat.device)
+            self._packed = self._empty_pack()
         if not self._pack_frozen:
             self._pack_into(self._packed)
         return self._packed
 
-    def _pack_into(self, out):
-        rc = N.lib().bcnf_pack_params(self._pdesc, N.ptr(self.flat), N.ptr(self.qflat), N.ptr(out),
-                                      N.stream_handle(self.flat.device))
-        N.check(rc, "bcnf_pack_params")
+    def _empty_pack(self):
+        return torch.empty(self._packed_bytes() // 4, dtype=torch.float32, device=self.flat.device)
 
     class _Reuse:
         def __init__(self, stack):
@@ -180,19 +167,30 @@ class FusedStack:
 
     def reuse_pack(self):
         """Pack once and reuse it for every launch inside the block (e.g. all chunks of sample())."""
-        return FusedStack._Reuse(self)
+        return StackBase._Reuse(self)
 
+    # ------------------------------------------------------------------ dropout RNG state
     # A feature network bound to this stack draws its dropout from the same (seed, offset) and leaves the advance to
     # the coupling launch that follows in the step (feature_network.py). True between such a feature draw and the
     # next coupling launch: a second feature draw before any coupling launch (the feature network run on its own)
     # advances the offset itself first (feature_rng_state), so repeated standalone calls draw fresh masks.
     _feature_pending = False
 
+    def _dropping(self, training: bool) -> bool:
+        """Whether a launch in this mode draws dropout masks (and so takes an rng_state())."""
+        return bool(training) and self.cfg.dropout > 0.0
+
     def rng_state(self):
         """Device-resident (seed, offset) for the in-kernel Philox dropout; the offset is bumped by a
         device-side add after every training forward, so HIP-graph replays draw fresh masks."""
         self._feature_pending = False          # a coupling launch takes this step's offset
         return self._rng_tensor()
+
+    @staticmethod
+    def _advance_rng(rng):
+        """The post-launch offset bump of a launch that drew masks from `rng` (None: it drew none)."""
+        if rng is not None:
+            rng[1:2].add_(1)
 
     def feature_rng_state(self):
         """The state a bound feature network's fused dropout draws from, when the coupling launch of the step will
@@ -215,146 +213,191 @@ class FusedStack:
         self.seed = int(seed)
         self._rng_state = None
 
-    def workspace_bytes(self, batch: int, training: bool):
-        L = N.lib()
-        wb = N.query_i64(L.bcnf_workspace_bytes, self._pdesc, ctypes.c_int64(batch), ctypes.c_int32(int(training)))
-        sb = N.query_i64(L.bcnf_slab_bytes, self._pdesc, ctypes.c_int64(batch))
-        return wb, sb
+    # ------------------------------------------------------------------ TrainStep's hooks
+    # Hybrid loss (_HybridNLL). hybrid_cot = (cotangent of vals, [c0 / (1 + w), c1, 0], w): TrainStep's constant
+    # cotangent and its stack form, so the backward launches no kernel to derive one from the other. hybrid_judge:
+    # False in a data-parallel TrainStep, where the all-reduced loss is judged (bcnf_guard_check_global), not the shard's.
+    hybrid_cot = None
+    hybrid_judge = True
 
-    # ------------------------------------------------------------------ launches
-    def launch_forward(self, y, h, training: bool, save: bool, want_logp: bool = False):
-        self._check_inputs(y, h, "forward")
-        if h.shape[0] != y.shape[0]:
-            raise ValueError(f"bcnf_amd forward: {y.shape[0]} samples but {h.shape[0]} feature rows")
-        B = y.shape[0]
-        dev = y.device
-        z = torch.empty_like(y)
-        ldj = torch.empty(B, dtype=torch.float32, device=dev)
-        logp = torch.empty(B, dtype=torch.float32, device=dev) if want_logp else None
-        drop = training and self.cfg.dropout > 0.0
-        rng = self.rng_state() if drop else None
-        wb, _ = self.workspace_bytes(B, training)      # also holds the condition projection
-        ws = torch.empty(max(wb // 4, 1), dtype=torch.float32, device=dev)
-        pk = self.packed(fresh=save)
-        tm = self.timers
-        if tm is not None:
+    def hybrid_guard(self):
+        return self.guard if self.hybrid_judge else None
+
+    # ------------------------------------------------------------------ inverse
+    def _check_ldj(self, training: bool):
+        """The density of a draw exists only where the inverse is the forward's inverse and deterministic."""
+        if self.cfg.two_way:
+            raise ValueError("bcnf_amd: no log-density for two_way stacks: the reference's two_way inverse "
+                             "(cnf.py:198-213) is not the inverse of its forward")
+        if self._dropping(training):
+            raise ValueError("bcnf_amd: no log-density for a training-mode inverse with dropout > 0 (the draw is not "
+                             "deterministic); call model.eval() first")
+
+    def launch_inverse(self, z, h, cond_index=None, training: bool = False, want_ldj: bool = False):
+        """y = inverse(z | h). want_ldj=True (eval, one-way): (y, ldj, log_prob) with ldj = log|det dz/dy| at the
+        returned y (what launch_forward(y, h) gives) and log_prob = -0.5 |z|^2 + ldj - D/2 log 2pi, from the same
+        launch; y is bit-identical to the plain call. The family supplies `_inverse_scratch_bytes`,
+        `_native_inverse` and `_native_inverse_logdet`."""
+        if want_ldj:
+            self._check_ldj(training)
+        self._check_inputs(z, h, "inverse")
+        n = z.shape[0]
+        if cond_index is None and h.shape[0] != n:
+            raise ValueError(f"bcnf_amd inverse: {n} latents but {h.shape[0]} feature rows and no cond_index")
+        y = torch.empty_like(z)
+        rng = self.rng_state() if self._dropping(training) else None
+        if cond_index is not None:
+            cond_index = cond_index.to(device=z.device, dtype=torch.int64).contiguous()
+        sb = self._inverse_scratch_bytes(h.shape[0], n)
+        scratch = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=z.device)
+        if want_ldj:
+            ldj = torch.empty(n, dtype=torch.float32, device=z.device)
+            logp = torch.empty(n, dtype=torch.float32, device=z.device)
+            return self._native_inverse_logdet(z, h, cond_index, y, training, ldj, logp, scratch)
+        self._native_inverse(z, h, cond_index, y, training, rng, scratch)
+        self._advance_rng(rng)
+        return y
+
+    # ------------------------------------------------------------------ kernel timing
+    @staticmethod
+    def _time_calls(calls, iters):
+        """{key: (entry point, *arguments)} -> {key: average device time (us)}, measured with HIP events on the launch
+        stream around `iters` back-to-back launches of the same (idempotent) call, so host launch latency is
+        amortised."""
+        out = {}
+        for key, launch in calls.items():
+            N.call(*launch)                           # warm (code object, LDS attributes)
             e0 = torch.cuda.Event(enable_timing=True)
             e1 = torch.cuda.Event(enable_timing=True)
             e0.record()
-        rc = N.lib().bcnf_stack_forward(self._pdesc, N.ptr(pk), N.ptr(y), N.ptr(h), ctypes.c_int64(B), N.ptr(z),
-                                        N.ptr(ldj), N.ptr(logp), ctypes.c_int32(int(training)), N.ptr(rng), N.ptr(ws),
-                                        ctypes.c_int32(int(save)), N.stream_handle(dev))
-        N.check(rc, "bcnf_stack_forward")
-        if tm is not None:
+            for _ in range(iters):
+                N.call_raw(*launch)
             e1.record()
-            tm.setdefault("k_forward", []).append((e0, e1))
-        if drop:
-            rng[1:2].add_(1)
+            torch.cuda.synchronize()
+            out[key] = e0.elapsed_time(e1) * 1e3 / iters
+        return out
+
+
+class FusedStack(StackBase):
+    """The register-resident small family: drives the HIP kernels of bcnf_stack.hip. A training launch is built by a
+    `_*_call(s)` method, which validates, allocates and returns ((entry point, *arguments), results); `launch_*` runs
+    it and `time_kernels` times the same tuples."""
+
+    @property
+    def supported(self) -> bool:
+        return bool(N.call_raw("bcnf_stack_supported", self._pdesc))
+
+    def counts(self):
+        rc, (a, b) = N.query_status("bcnf_param_count", self._pdesc, outs=2)
+        N.check(rc, "bcnf_param_count")
+        return a, b
+
+    def flatten(self):
+        super().flatten()
+        self._raw_tables = {}
+
+    def _packed_bytes(self):
+        return N.query_i64("bcnf_packed_bytes", self._pdesc)
+
+    def _pack_into(self, out):
+        N.call("bcnf_pack_params", self._pdesc, self.flat, self.qflat, out, N.stream_handle(self.flat.device))
+
+    def workspace_bytes(self, batch: int, training: bool):
+        wb = N.query_i64("bcnf_workspace_bytes", self._pdesc, batch, training)
+        sb = N.query_i64("bcnf_slab_bytes", self._pdesc, batch)
+        return wb, sb
+
+    # ------------------------------------------------------------------ launches
+    def _forward_buffers(self, y, training):
+        """z, ldj, the dropout state (the pass's one rng_state() draw; None without dropout) and the workspace."""
+        B = y.shape[0]
+        z = torch.empty_like(y)
+        ldj = torch.empty(B, dtype=torch.float32, device=y.device)
+        rng = self.rng_state() if self._dropping(training) else None
+        wb, _ = self.workspace_bytes(B, training)      # also holds the condition projection
+        ws = torch.empty(max(wb // 4, 1), dtype=torch.float32, device=y.device)
+        return z, ldj, rng, ws
+
+    def _backward_buffers(self, h, slab_bytes, want_dy, want_dh):
+        slab = torch.empty(max(slab_bytes // 4, 1), dtype=torch.float32, device=h.device)
+        dparams = torch.empty_like(self.flat)
+        dh = torch.empty_like(h) if want_dh else None
+        dy = torch.empty((h.shape[0], self.cfg.size), dtype=torch.float32, device=h.device) if want_dy else None
+        return slab, dparams, dh, dy
+
+    def launch_forward(self, y, h, training: bool, save: bool, want_logp: bool = False):
+        self._check_forward(y, h)
+        B = y.shape[0]
+        z, ldj, rng, ws = self._forward_buffers(y, training)
+        logp = torch.empty(B, dtype=torch.float32, device=y.device) if want_logp else None
+        pk = self.packed(fresh=save)
+        N.call("bcnf_stack_forward", self._pdesc, pk, y, h, B, z, ldj, logp, training, rng, ws, save,
+               N.stream_handle(y.device))
+        self._advance_rng(rng)
         return z, ldj, logp, (ws, pk)
 
     def launch_backward(self, h, dz, dldj, training: bool, saved, want_dy: bool, want_dh: bool):
         ws, pk = saved
         B = h.shape[0]
-        dev = h.device
-        _, sb = self.workspace_bytes(B, training)
-        slab = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=dev)
-        dparams = torch.empty_like(self.flat)
-        dh = torch.empty_like(h) if want_dh else None
-        dy = torch.empty((B, self.cfg.size), dtype=torch.float32, device=dev) if want_dy else None
-        stream = N.stream_handle(dev)
-        tm = self.timers
-        e0 = None
-        if tm is not None:
-            e0 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        rc = N.lib().bcnf_stack_backward(self._pdesc, N.ptr(pk), N.ptr(h), N.ptr(dz), N.ptr(dldj),
-                                         ctypes.c_int64(B), ctypes.c_int32(int(training)), N.ptr(ws), N.ptr(dy),
-                                         None, None, N.ptr(slab), stream)
-        N.check(rc, "bcnf_stack_backward")
-        self._backward_tail(h, ws, pk, slab, dh, dparams, B, training, stream, tm, e0)
+        slab, dparams, dh, dy = self._backward_buffers(h, self.workspace_bytes(B, training)[1], want_dy, want_dh)
+        N.call("bcnf_stack_backward", self._pdesc, pk, h, dz, dldj, B, training, ws, dy, None, None, slab,
+               N.stream_handle(h.device))
+        N.call(*self._tail_call(h, saved, slab, training, dh, dparams))
         return dy, dh, dparams
 
-    def _backward_tail(self, h, ws, pk, slab, dh, dparams, B, training, stream, tm, e0):
+    def _tail_call(self, h, saved, slab, training, dh, dparams):
         """dL/dh and the deterministic parameter-gradient reduction after a backward launch (one fused tail
-        launch + the split-K finish); with timers, the backward and the tail get HIP-event pairs."""
-        if tm is not None:
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            tm.setdefault("k_backward", []).append((e0, e1))
-            e0 = e1
-        N.check(N.lib().bcnf_backward_tail(self._pdesc, N.ptr(pk), N.ptr(slab), N.ptr(h), N.ptr(ws), ctypes.c_int64(B),
-                                           ctypes.c_int32(int(training)), N.ptr(dh), N.ptr(dparams), stream),
-                "bcnf_backward_tail")
-        if tm is not None:
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            tm.setdefault("k_bwd_tail", []).append((e0, e1))
+        launch + the split-K finish)."""
+        ws, pk = saved
+        return ("bcnf_backward_tail", self._pdesc, pk, slab, h, ws, h.shape[0], training, dh, dparams,
+                N.stream_handle(h.device))
+
+    def _nll_forward_call(self, y, h, training, finalize):
+        self._check_forward(y, h)
+        B = y.shape[0]
+        if B == 0:
+            raise ValueError("bcnf_amd: the NLL of an empty batch is undefined")
+        z, ldj, rng, ws = self._forward_buffers(y, training)
+        vals = torch.empty(3, dtype=torch.float32, device=y.device)
+        pk = self.packed(fresh=True)
+        launch = ("bcnf_nll_forward", self._pdesc, pk, y, h, B, z, ldj, training, rng, ws, finalize, vals,
+                  self.guard if finalize else None, N.stream_handle(y.device))
+        return launch, (z, ldj, vals, (ws, pk))
 
     def launch_nll_forward(self, y, h, training: bool, finalize: bool = True):
         """Stack forward fused with inn_nll_loss (trainer.py:260-266): returns z, ldj, vals=[loss, nll, mse]
         and the saved state for launch_nll_backward. With finalize=False the loss reduction and the
         dropout-RNG advance are deferred to the backward (vals is valid only after it)."""
-        self._check_inputs(y, h, "forward")
-        if h.shape[0] != y.shape[0]:
-            raise ValueError(f"bcnf_amd forward: {y.shape[0]} samples but {h.shape[0]} feature rows")
-        B = y.shape[0]
-        if B == 0:
-            raise ValueError("bcnf_amd: the NLL of an empty batch is undefined")
-        dev = y.device
-        z = torch.empty_like(y)
-        ldj = torch.empty(B, dtype=torch.float32, device=dev)
-        vals = torch.empty(3, dtype=torch.float32, device=dev)
-        drop = training and self.cfg.dropout > 0.0
-        rng = self.rng_state() if drop else None
-        wb, _ = self.workspace_bytes(B, training)
-        ws = torch.empty(max(wb // 4, 1), dtype=torch.float32, device=dev)
-        pk = self.packed(fresh=True)
-        tm = self.timers
-        if tm is not None:
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        rc = N.lib().bcnf_nll_forward(self._pdesc, N.ptr(pk), N.ptr(y), N.ptr(h), ctypes.c_int64(B), N.ptr(z),
-                                      N.ptr(ldj), ctypes.c_int32(int(training)), N.ptr(rng), N.ptr(ws),
-                                      ctypes.c_int32(int(finalize)), N.ptr(vals), N.ptr(self.guard if finalize else None),
-                                      N.stream_handle(dev))
-        N.check(rc, "bcnf_nll_forward")
-        if tm is not None:
-            e1.record()
-            tm.setdefault("k_forward", []).append((e0, e1))
-        return z, ldj, vals, (ws, pk)
+        launch, out = self._nll_forward_call(y, h, training, finalize)
+        N.call(*launch)
+        return out
+
+    def _nll_backward_call(self, rows, z, dvals, training, saved, slab, dy, finalize_into):
+        """The fused NLL backward over `rows` (the features h, or the folded pass's x). finalize_into: the deferred
+        loss reduction and dropout-RNG advance of the forward run in this launch."""
+        ws, pk = saved
+        rng = self.rng_state() if (finalize_into is not None and self._dropping(training)) else None
+        return ("bcnf_nll_backward", self._pdesc, pk, rows, z, dvals, rows.shape[0], training, ws, dy, None, None, slab,
+                finalize_into, rng, self.guard if finalize_into is not None else None, N.stream_handle(rows.device))
+
+    def _nll_backward_calls(self, h, z, dvals, training, saved, want_dy, want_dh, finalize_into=None):
+        slab, dparams, dh, dy = self._backward_buffers(h, self.workspace_bytes(h.shape[0], training)[1], want_dy,
+                                                       want_dh)
+        return ((self._nll_backward_call(h, z, dvals, training, saved, slab, dy, finalize_into),
+                 self._tail_call(h, saved, slab, training, dh, dparams)), (dy, dh, dparams))
 
     def launch_nll_backward(self, h, z, dvals, training: bool, saved, want_dy: bool, want_dh: bool,
                             finalize_into=None):
-        ws, pk = saved
-        B = h.shape[0]
-        dev = h.device
-        _, sb = self.workspace_bytes(B, training)
-        slab = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=dev)
-        dparams = torch.empty_like(self.flat)
-        dh = torch.empty_like(h) if want_dh else None
-        dy = torch.empty((B, self.cfg.size), dtype=torch.float32, device=dev) if want_dy else None
-        stream = N.stream_handle(dev)
-        tm = self.timers
-        e0 = None
-        if tm is not None:
-            e0 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        rng = self.rng_state() if (finalize_into is not None and training and self.cfg.dropout > 0.0) else None
-        rc = N.lib().bcnf_nll_backward(self._pdesc, N.ptr(pk), N.ptr(h), N.ptr(z), N.ptr(dvals), ctypes.c_int64(B),
-                                       ctypes.c_int32(int(training)), N.ptr(ws), N.ptr(dy), None, None,
-                                       N.ptr(slab), N.ptr(finalize_into), N.ptr(rng),
-                                       N.ptr(self.guard if finalize_into is not None else None), stream)
-        N.check(rc, "bcnf_nll_backward")
-        self._backward_tail(h, ws, pk, slab, dh, dparams, B, training, stream, tm, e0)
-        return dy, dh, dparams
+        launches, out = self._nll_backward_calls(h, z, dvals, training, saved, want_dy, want_dh, finalize_into)
+        for launch in launches:
+            N.call(*launch)
+        return out
 
     # ------------------------------------------------------------------ folded linear feature network
     def fold_supported(self, in_features: int) -> bool:
         """Whether a single nn.Linear [in_features -> n_conditions] feature network can be folded into the
         condition projection (bcnf_pack_params_fold; include/bcnf_amd.h)."""
-        out = ctypes.c_int64(0)
-        return N.lib().bcnf_fold_bytes(self._pdesc, ctypes.c_int32(int(in_features)), ctypes.byref(out)) == N.OK
+        return N.query_status("bcnf_fold_bytes", self._pdesc, int(in_features))[0] == N.OK
 
     # bcnf_fold_train_forward (the pack-free folded forward, one launch) where its table applies; False: always the
     # two-launch form (pack + fold, then the forward) -- BCNF_FOLD_RAW=0 in the environment, for A/B runs
@@ -370,16 +413,39 @@ class FusedStack:
         if key not in self._raw_tables:
             if torch.cuda.is_current_stream_capturing():
                 return None                     # no host -> device copy inside a graph capture
-            L = N.lib()
-            nb = ctypes.c_int64(0)
-            if L.bcnf_fold_raw_table_bytes(self._pdesc, ctypes.c_int32(X), ctypes.byref(nb)) != N.OK:
+            rc, (nb,) = N.query_status("bcnf_fold_raw_table_bytes", self._pdesc, X)
+            if rc != N.OK:
                 self._raw_tables[key] = None
             else:
-                host = torch.empty(nb.value // 4, dtype=torch.int32)
-                N.check(L.bcnf_fold_raw_table(self._pdesc, ctypes.c_int32(X), ctypes.c_void_p(host.data_ptr())),
-                        "bcnf_fold_raw_table")
+                host = torch.empty(nb // 4, dtype=torch.int32)
+                N.call("bcnf_fold_raw_table", self._pdesc, X, host)
                 self._raw_tables[key] = host.to(dev)
         return self._raw_tables[key]
+
+    def _fold_forward_calls(self, y, x, wf, bf, training, finalize, gather):
+        self._check_device(y, x, wf, bf)
+        B, X = x.shape
+        if y.dim() != 2 or y.shape != (B, self.cfg.size):
+            raise ValueError(f"bcnf_amd folded forward: y {tuple(y.shape)} vs x {tuple(x.shape)}")
+        if B == 0:
+            raise ValueError("bcnf_amd: the NLL of an empty batch is undefined")
+        stream = N.stream_handle(y.device)
+        pk = self._empty_pack()
+        table = self.raw_table(X)
+        z, ldj, rng, ws = self._forward_buffers(y, training)
+        vals = torch.empty(3, dtype=torch.float32, device=y.device)
+        guard = self.guard if finalize else None
+        if table is not None:
+            launches = (("bcnf_fold_train_forward", self._pdesc, self.flat, self.qflat, table, wf, bf, X, gather, y, x,
+                         x.stride(0), B, pk, z, ldj, training, rng, ws, finalize, vals, guard, stream),)
+        else:
+            fold = torch.empty(N.query_i64("bcnf_fold_bytes", self._pdesc, X) // 4, dtype=torch.float32,
+                               device=y.device)
+            launches = (("bcnf_pack_params_fold", self._pdesc, self.flat, self.qflat, wf, bf, X, pk, fold, gather,
+                         stream),
+                        ("bcnf_fold_nll_forward", self._pdesc, pk, fold, X, y, x, x.stride(0), B, z, ldj, training,
+                         rng, ws, finalize, vals, guard, stream))
+        return launches, (z, ldj, vals, (ws, pk))
 
     def launch_fold_nll_forward(self, y, x, wf, bf, training: bool, finalize: bool = True, gather=None):
         """launch_nll_forward with h = x Wf^T + bf never formed as a tensor. Pack-free form (raw_table applies):
@@ -387,60 +453,10 @@ class FusedStack:
         on the fly. Otherwise the pack launch also folds the Linear into the projection weights (Wc = W1h Wf,
         bc = b1 + W1h bf) and the projection runs on x. gather (an N.BcnfGather2 that fills y and x): the batch
         gather runs inside the first launch."""
-        self._check_device(y, x, wf, bf)
-        B, X = x.shape
-        if y.dim() != 2 or y.shape != (B, self.cfg.size):
-            raise ValueError(f"bcnf_amd folded forward: y {tuple(y.shape)} vs x {tuple(x.shape)}")
-        if B == 0:
-            raise ValueError("bcnf_amd: the NLL of an empty batch is undefined")
-        L = N.lib()
-        dev = y.device
-        stream = N.stream_handle(dev)
-        pk = torch.empty(N.query_i64(L.bcnf_packed_bytes, self._pdesc) // 4, dtype=torch.float32, device=dev)
-        table = self.raw_table(X)
-        if table is not None:
-            z = torch.empty_like(y)
-            ldj = torch.empty(B, dtype=torch.float32, device=dev)
-            vals = torch.empty(3, dtype=torch.float32, device=dev)
-            rng = self.rng_state() if (training and self.cfg.dropout > 0.0) else None
-            wb, _ = self.workspace_bytes(B, training)
-            ws = torch.empty(max(wb // 4, 1), dtype=torch.float32, device=dev)
-            rc = L.bcnf_fold_train_forward(self._pdesc, N.ptr(self.flat), N.ptr(self.qflat), N.ptr(table), N.ptr(wf),
-                                           N.ptr(bf), ctypes.c_int32(X),
-                                           None if gather is None else ctypes.byref(gather), N.ptr(y), N.ptr(x),
-                                           ctypes.c_int32(x.stride(0)), ctypes.c_int64(B), N.ptr(pk), N.ptr(z),
-                                           N.ptr(ldj), ctypes.c_int32(int(training)), N.ptr(rng), N.ptr(ws),
-                                           ctypes.c_int32(int(finalize)), N.ptr(vals),
-                                           N.ptr(self.guard if finalize else None), stream)
-            N.check(rc, "bcnf_fold_train_forward")
-            return z, ldj, vals, (ws, pk)
-        fold = torch.empty(N.query_i64(L.bcnf_fold_bytes, self._pdesc, ctypes.c_int32(X)) // 4, dtype=torch.float32,
-                           device=dev)
-        N.check(L.bcnf_pack_params_fold(self._pdesc, N.ptr(self.flat), N.ptr(self.qflat), N.ptr(wf), N.ptr(bf),
-                                        ctypes.c_int32(X), N.ptr(pk), N.ptr(fold),
-                                        None if gather is None else ctypes.byref(gather), stream),
-                "bcnf_pack_params_fold")
-        z = torch.empty_like(y)
-        ldj = torch.empty(B, dtype=torch.float32, device=dev)
-        vals = torch.empty(3, dtype=torch.float32, device=dev)
-        rng = self.rng_state() if (training and self.cfg.dropout > 0.0) else None
-        wb, _ = self.workspace_bytes(B, training)
-        ws = torch.empty(max(wb // 4, 1), dtype=torch.float32, device=dev)
-        rc = L.bcnf_fold_nll_forward(self._pdesc, N.ptr(pk), N.ptr(fold), ctypes.c_int32(X), N.ptr(y), N.ptr(x),
-                                     ctypes.c_int32(x.stride(0)), ctypes.c_int64(B), N.ptr(z), N.ptr(ldj), ctypes.c_int32(int(training)),
-                                     N.ptr(rng), N.ptr(ws), ctypes.c_int32(int(finalize)), N.ptr(vals),
-                                     N.ptr(self.guard if finalize else None), stream)
-        N.check(rc, "bcnf_fold_nll_forward")
-        return z, ldj, vals, (ws, pk)
-
-    # Hybrid loss (_HybridNLL). hybrid_cot = (cotangent of vals, [c0 / (1 + w), c1, 0], w): TrainStep's constant
-    # cotangent and its stack form, so the backward launches no kernel to derive one from the other. hybrid_judge:
-    # False in a data-parallel TrainStep, where the all-reduced loss is judged (bcnf_guard_check_global), not the shard's.
-    hybrid_cot = None
-    hybrid_judge = True
-
-    def hybrid_guard(self):
-        return self.guard if self.hybrid_judge else None
+        launches, out = self._fold_forward_calls(y, x, wf, bf, training, finalize, gather)
+        for launch in launches:
+            N.call(*launch)
+        return out
 
     # A BcnfFoldAdam for the next folded backward (TrainStep, multi-step graphs): consumed by that launch.
     pending_adam = None
@@ -448,17 +464,11 @@ class FusedStack:
     # the folded backward writes its gradients into.
     grad_bucket = None
 
-    def launch_fold_nll_backward(self, x, z, dvals, wf, bf, training: bool, saved, want_feat: bool,
-                                 finalize_into=None, adam=None):
-        """Fused NLL backward of the folded pass: (dparams, dWf, dbf); no dL/dh, no dL/dx. adam (an
-        N.BcnfFoldAdam): the optimizer update of every parameter runs inside the backward tail."""
+    def _fold_backward_calls(self, x, z, dvals, wf, bf, training, saved, want_feat, finalize_into=None, adam=None):
         ws, pk = saved
         B, X = x.shape
-        L = N.lib()
-        dev = x.device
-        stream = N.stream_handle(dev)
-        sb = N.query_i64(L.bcnf_fold_slab_bytes, self._pdesc, ctypes.c_int32(X), ctypes.c_int64(B))
-        slab = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=dev)
+        sb = N.query_i64("bcnf_fold_slab_bytes", self._pdesc, X, B)
+        slab = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=x.device)
         gb = self.grad_bucket
         if gb is not None and want_feat:
             # data parallel (TrainStep): the gradients land in the all-reduce bucket itself, as fresh views that
@@ -471,158 +481,58 @@ class FusedStack:
             dparams = torch.empty_like(self.flat)
             dwf = torch.empty_like(wf) if want_feat else None
             dbf = torch.empty_like(bf) if (want_feat and bf is not None) else None
-        rng = self.rng_state() if (finalize_into is not None and training and self.cfg.dropout > 0.0) else None
-        rc = L.bcnf_nll_backward(self._pdesc, N.ptr(pk), N.ptr(x), N.ptr(z), N.ptr(dvals), ctypes.c_int64(B),
-                                 ctypes.c_int32(int(training)), N.ptr(ws), None, None, None, N.ptr(slab),
-                                 N.ptr(finalize_into), N.ptr(rng),
-                                 N.ptr(self.guard if finalize_into is not None else None), stream)
-        N.check(rc, "bcnf_nll_backward")
-        N.check(L.bcnf_fold_backward_tail(self._pdesc, N.ptr(pk), N.ptr(slab), N.ptr(x), ctypes.c_int32(x.stride(0)),
-                                          ctypes.c_int32(X), N.ptr(wf),
-                                          N.ptr(bf), N.ptr(ws), ctypes.c_int64(B), ctypes.c_int32(int(training)),
-                                          N.ptr(dparams), N.ptr(dwf), N.ptr(dbf),
-                                          None if adam is None else ctypes.byref(adam), stream),
-                "bcnf_fold_backward_tail")
-        return dparams, dwf, dbf
+        tail = ("bcnf_fold_backward_tail", self._pdesc, pk, slab, x, x.stride(0), X, wf, bf, ws, B, training, dparams,
+                dwf, dbf, adam, N.stream_handle(x.device))
+        return ((self._nll_backward_call(x, z, dvals, training, saved, slab, None, finalize_into), tail),
+                (dparams, dwf, dbf))
+
+    def launch_fold_nll_backward(self, x, z, dvals, wf, bf, training: bool, saved, want_feat: bool,
+                                 finalize_into=None, adam=None):
+        """Fused NLL backward of the folded pass: (dparams, dWf, dbf); no dL/dh, no dL/dx. adam (an
+        N.BcnfFoldAdam): the optimizer update of every parameter runs inside the backward tail."""
+        launches, out = self._fold_backward_calls(x, z, dvals, wf, bf, training, saved, want_feat, finalize_into, adam)
+        for launch in launches:
+            N.call(*launch)
+        return out
 
     @torch.no_grad()
     def time_kernels(self, y, h, training: bool = True, iters: int = 20, fold=None):
-        """Average device time (us) of each launch of one NLL training pass, measured with HIP events on the
-        launch stream around `iters` back-to-back launches of the same (idempotent) call, so host launch
-        latency is amortised: 'forward' (k_hp + k_forward), 'k_backward' (the backward kernel alone) and
-        'tail' (dh + slab reduce + W1 condition part). fold = (x, Wf, bf): the folded path instead -- 'pack'
-        (pack + fold), 'forward' (k_hp on x + k_forward), 'k_backward', 'tail' (slab reduce + split-K on x,
-        Gx reduce, dW1h / dWf / dbf)."""
-        if fold is not None:
-            return self._time_fold_kernels(y, *fold, training=training, iters=iters)
-        L = N.lib()
-        dev = y.device
-        stream = N.stream_handle(dev)
-        B = y.shape[0]
-        z, _, vals, (ws, pk) = self.launch_nll_forward(y, h, training, finalize=False)
-        _, sb = self.workspace_bytes(B, training)
-        slab = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=dev)
-        dh = torch.empty_like(h)
-        dparams = torch.empty_like(self.flat)
-        ldj = torch.empty(B, dtype=torch.float32, device=dev)
-        rng = self.rng_state() if (training and self.cfg.dropout > 0.0) else None
-        calls = {
-            "k_forward": lambda: L.bcnf_nll_forward(self._pdesc, N.ptr(pk), N.ptr(y), N.ptr(h), ctypes.c_int64(B), N.ptr(z),
-                                                  N.ptr(ldj), ctypes.c_int32(int(training)), N.ptr(rng), N.ptr(ws),
-                                                  ctypes.c_int32(0), N.ptr(vals), None, stream),
-            "k_backward": lambda: L.bcnf_nll_backward(self._pdesc, N.ptr(pk), N.ptr(h), N.ptr(z), None, ctypes.c_int64(B),
-                                                      ctypes.c_int32(int(training)), N.ptr(ws), None, None, None,
-                                                      N.ptr(slab), None, None, None, stream),
-            "tail": lambda: L.bcnf_backward_tail(self._pdesc, N.ptr(pk), N.ptr(slab), N.ptr(h), N.ptr(ws),
-                                                 ctypes.c_int64(B), ctypes.c_int32(int(training)), N.ptr(dh),
-                                                 N.ptr(dparams), stream),
-        }
-        return self._event_times(calls, iters)
+        """Average device time (us) of each launch of one NLL training pass (_time_calls), the reduction deferred and
+        never run, so no call advances the dropout offset: 'k_forward' (k_hp + k_forward), 'k_backward' (the backward
+        kernel alone) and 'tail' (dh + slab reduce + W1 condition part). fold = (x, Wf, bf): the folded path instead
+        -- 'k_pack_fold' (pack + fold; absent where the pack-free forward applies), 'k_forward' (k_hp on x +
+        k_forward), 'k_backward', 'tail' (slab reduce + split-K on x, Gx reduce, dW1h / dWf / dbf)."""
+        if fold is None:
+            forward, (z, _, _, saved) = self._nll_forward_call(y, h, training, finalize=False)
+            (backward, tail), _ = self._nll_backward_calls(h, z, None, training, saved, want_dy=False, want_dh=True)
+            calls = {"k_forward": forward}
+        else:
+            x, wf, bf = fold
+            forwards, (z, _, _, saved) = self._fold_forward_calls(y, x, wf, bf, training, finalize=False, gather=None)
+            (backward, tail), _ = self._fold_backward_calls(x, z, None, wf, bf, training, saved, want_feat=True)
+            calls = dict(zip(("k_pack_fold", "k_forward")[-len(forwards):], forwards))
+        calls.update(k_backward=backward, tail=tail)
+        return self._time_calls(calls, iters)
 
-    @staticmethod
-    def _event_times(calls, iters):
-        out = {}
-        for name, fn in calls.items():
-            N.check(fn(), name)                       # warm (code object, LDS attributes)
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            out[name] = e0.elapsed_time(e1) * 1e3 / iters
-        return out
+    # ------------------------------------------------------------------ inverse (StackBase.launch_inverse)
+    def _inverse_scratch_bytes(self, feature_rows, n):
+        return N.query_i64("bcnf_inverse_scratch_bytes", self._pdesc, feature_rows)
 
-    def _time_fold_kernels(self, y, x, wf, bf, training: bool, iters: int):
-        L = N.lib()
-        dev = y.device
-        stream = N.stream_handle(dev)
-        B, X = x.shape
-        ldx = ctypes.c_int32(x.stride(0))
-        z, _, vals, (ws, pk) = self.launch_fold_nll_forward(y, x, wf, bf, training, finalize=False)
-        fold = torch.empty(N.query_i64(L.bcnf_fold_bytes, self._pdesc, ctypes.c_int32(X)) // 4, dtype=torch.float32,
-                           device=dev)
-        N.check(L.bcnf_pack_params_fold(self._pdesc, N.ptr(self.flat), N.ptr(self.qflat), N.ptr(wf), N.ptr(bf),
-                                        ctypes.c_int32(X), N.ptr(pk), N.ptr(fold), None, stream), "pack_fold")
-        sb = N.query_i64(L.bcnf_fold_slab_bytes, self._pdesc, ctypes.c_int32(X), ctypes.c_int64(B))
-        slab = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=dev)
-        dparams = torch.empty_like(self.flat)
-        dwf, dbf = torch.empty_like(wf), (torch.empty_like(bf) if bf is not None else None)
-        ldj = torch.empty(B, dtype=torch.float32, device=dev)
-        rng = self.rng_state() if (training and self.cfg.dropout > 0.0) else None
-        table = self.raw_table(X)
-        calls = {
-            "k_pack_fold": lambda: L.bcnf_pack_params_fold(self._pdesc, N.ptr(self.flat), N.ptr(self.qflat), N.ptr(wf),
-                                                    N.ptr(bf), ctypes.c_int32(X), N.ptr(pk), N.ptr(fold), None, stream),
-            "k_forward": lambda: L.bcnf_fold_nll_forward(self._pdesc, N.ptr(pk), N.ptr(fold), ctypes.c_int32(X),
-                                                       N.ptr(y), N.ptr(x), ldx, ctypes.c_int64(B), N.ptr(z),
-                                                       N.ptr(ldj), ctypes.c_int32(int(training)), N.ptr(rng),
-                                                       N.ptr(ws), ctypes.c_int32(0), N.ptr(vals), None, stream),
-            "k_backward": lambda: L.bcnf_nll_backward(self._pdesc, N.ptr(pk), N.ptr(x), N.ptr(z), None,
-                                                      ctypes.c_int64(B), ctypes.c_int32(int(training)), N.ptr(ws),
-                                                      None, None, None, N.ptr(slab), None, None, None, stream),
-            "tail": lambda: L.bcnf_fold_backward_tail(self._pdesc, N.ptr(pk), N.ptr(slab), N.ptr(x), ldx,
-                                                      ctypes.c_int32(X), N.ptr(wf), N.ptr(bf), N.ptr(ws),
-                                                      ctypes.c_int64(B), ctypes.c_int32(int(training)),
-                                                      N.ptr(dparams), N.ptr(dwf), N.ptr(dbf), None, stream),
-        }
-        if table is not None:           # the pack-free forward: no pack launch
-            del calls["k_pack_fold"]
-            calls["k_forward"] = lambda: L.bcnf_fold_train_forward(
-                self._pdesc, N.ptr(self.flat), N.ptr(self.qflat), N.ptr(table), N.ptr(wf), N.ptr(bf), ctypes.c_int32(X),
-                None, N.ptr(y), N.ptr(x), ldx, ctypes.c_int64(B), N.ptr(pk), N.ptr(z), N.ptr(ldj),
-                ctypes.c_int32(int(training)), N.ptr(rng), N.ptr(ws), ctypes.c_int32(0), N.ptr(vals), None, stream)
-        return self._event_times(calls, iters)
+    def _native_inverse(self, z, h, cond_index, y, training, rng, scratch):
+        N.call("bcnf_stack_inverse", self._pdesc, self.packed(), z, h, h.shape[0], cond_index, z.shape[0], y, training,
+               rng, scratch, N.stream_handle(z.device))
 
-    def _check_ldj(self, training: bool):
-        """The density of a draw exists only where the inverse is the forward's inverse and deterministic."""
-        if self.cfg.two_way:
-            raise ValueError("bcnf_amd: no log-density for two_way stacks: the reference's two_way inverse "
-                             "(cnf.py:198-213) is not the inverse of its forward")
-        if training and self.cfg.dropout > 0.0:
-            raise ValueError("bcnf_amd: no log-density for a training-mode inverse with dropout > 0 (the draw is not "
-                             "deterministic); call model.eval() first")
-
-    def launch_inverse(self, z, h, cond_index=None, training: bool = False, want_ldj: bool = False):
-        """y = inverse(z | h). want_ldj=True (eval, one-way): (y, ldj, log_prob) with ldj = log|det dz/dy| at the
-        returned y (what launch_forward(y, h) gives) and log_prob = -0.5 |z|^2 + ldj - D/2 log 2pi, from the same
-        launch; y is bit-identical to the plain call."""
-        if want_ldj:
-            self._check_ldj(training)
-        self._check_inputs(z, h, "inverse")
-        n = z.shape[0]
-        if cond_index is None and h.shape[0] != n:
-            raise ValueError(f"bcnf_amd inverse: {n} latents but {h.shape[0]} feature rows and no cond_index")
-        y = torch.empty_like(z)
-        drop = training and self.cfg.dropout > 0.0
-        rng = self.rng_state() if drop else None
-        if cond_index is not None:
-            cond_index = cond_index.to(device=z.device, dtype=torch.int64).contiguous()
-        hr = h.shape[0]
-        sb = N.query_i64(N.lib().bcnf_inverse_scratch_bytes, self._pdesc, ctypes.c_int64(hr))
-        scratch = torch.empty(max(sb // 4, 1), dtype=torch.float32, device=z.device)
-        if want_ldj:
-            ldj = torch.empty(n, dtype=torch.float32, device=z.device)
-            logp = torch.empty(n, dtype=torch.float32, device=z.device)
-            rc = N.lib().bcnf_stack_inverse_logdet(self._pdesc, N.ptr(self.packed()), N.ptr(z), N.ptr(h),
-                                                   ctypes.c_int64(hr), N.ptr(cond_index), ctypes.c_int64(n), N.ptr(y),
-                                                   N.ptr(ldj), N.ptr(logp), N.ptr(scratch), N.stream_handle(z.device))
-            if rc == N.ERR_UNSUPPORTED:
-                # a layout outside the matrix-core inverse: the plain inverse, then the forward kernels at y
-                y = self.launch_inverse(z, h, cond_index, training)
-                hh = h if cond_index is None else h.index_select(0, cond_index)
-                _, ldj, _, _ = self.launch_forward(y, hh.contiguous(), False, save=False)
-                return y, ldj, log_prob_of_latent(z, ldj)
-            N.check(rc, "bcnf_stack_inverse_logdet")
-            return y, ldj, logp
-        rc = N.lib().bcnf_stack_inverse(self._pdesc, N.ptr(self.packed()), N.ptr(z), N.ptr(h), ctypes.c_int64(hr),
-                                        N.ptr(cond_index), ctypes.c_int64(n), N.ptr(y), ctypes.c_int32(int(training)),
-                                        N.ptr(rng), N.ptr(scratch), N.stream_handle(z.device))
-        N.check(rc, "bcnf_stack_inverse")
-        if drop:
-            rng[1:2].add_(1)
-        return y
+    def _native_inverse_logdet(self, z, h, cond_index, y, training, ldj, logp, scratch):
+        rc = N.call_raw("bcnf_stack_inverse_logdet", self._pdesc, self.packed(), z, h, h.shape[0], cond_index,
+                           z.shape[0], y, ldj, logp, scratch, N.stream_handle(z.device))
+        if rc == N.ERR_UNSUPPORTED:
+            # a layout outside the matrix-core inverse: the plain inverse, then the forward kernels at y
+            y = self.launch_inverse(z, h, cond_index, training)
+            hh = h if cond_index is None else h.index_select(0, cond_index)
+            _, ldj, _, _ = self.launch_forward(y, hh.contiguous(), False, save=False)
+            return y, ldj, log_prob_of_latent(z, ldj)
+        N.check(rc, "bcnf_stack_inverse_logdet")
+        return y, ldj, logp
 
 
 class _StackForward(torch.autograd.Function):
@@ -630,7 +540,7 @@ class _StackForward(torch.autograd.Function):
     whole flat parameter gradient (one AccumulateGrad for `flat_param`)."""
 
     @staticmethod
-    def forward(ctx, y, h, flat_param, stack: FusedStack, training: bool):
+    def forward(ctx, y, h, flat_param, stack: StackBase, training: bool):
         needs = ctx.needs_input_grad
         save = any(needs[:3])
         z, ldj, _, saved = stack.launch_forward(y, h, training, save=save)
@@ -658,7 +568,7 @@ class _StackNLL(torch.autograd.Function):
     backward (no dz / dldj tensors, no elementwise loss kernels)."""
 
     @staticmethod
-    def forward(ctx, y, h, flat_param, stack: FusedStack, training: bool, defer: bool):
+    def forward(ctx, y, h, flat_param, stack: StackBase, training: bool, defer: bool):
         z, _, vals, saved = stack.launch_nll_forward(y, h, training, finalize=not defer)
         ctx.stack = stack
         ctx.training = training
@@ -677,7 +587,7 @@ class _StackNLL(torch.autograd.Function):
         return dy, dh, (dparams if need_p else None), None, None, None
 
 
-def stack_nll(stack: FusedStack, y, h, training: bool, defer: bool = False):
+def stack_nll(stack: StackBase, y, h, training: bool, defer: bool = False):
     """[loss, nll, mse] (mse = 0, hybrid_weight = 0) of the Trainer's loss on the fused stack. defer=True
     (for a backward that certainly follows, e.g. TrainStep) lets the backward do the loss reduction and
     the dropout-RNG advance: one launch less, but vals is only valid after the backward."""
@@ -694,34 +604,25 @@ def stack_nll(stack: FusedStack, y, h, training: bool, defer: bool = False):
 def head_workspace(B: int, K: int, D: int, device):
     """Caller-owned workspace of the prediction-head kernels (bcnf_head_work_bytes): residual, MSE partials, split-K
     partials of dW / dbias."""
-    nbytes = N.query_i64(N.lib().bcnf_head_work_bytes, ctypes.c_int64(B), ctypes.c_int32(K), ctypes.c_int32(D))
-    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    return torch.empty(N.query_i64("bcnf_head_work_bytes", B, K, D) // 4, dtype=torch.float32, device=device)
 
 
 def launch_head_forward(h, wp, bp, y, work):
     """r = h Wp^T + bp - y and the squared-error partials into `work` (bcnf_head_mse_forward)."""
     B, K = h.shape
-    N.check(N.lib().bcnf_head_mse_forward(N.ptr(h), ctypes.c_int64(h.stride(0)), ctypes.c_int32(K), N.ptr(wp),
-                                          N.ptr(bp), N.ptr(y), ctypes.c_int64(B), ctypes.c_int32(y.shape[1]),
-                                          N.ptr(work), N.stream_handle(h.device)), "bcnf_head_mse_forward")
+    N.call("bcnf_head_mse_forward", h, h.stride(0), K, wp, bp, y, B, y.shape[1], work, N.stream_handle(h.device))
 
 
 def launch_head_backward(h, wp, work, dvals, weight: float, D: int, dwp, dbp, dh, accumulate: bool):
     """dWp, dbp and dL/dh (added into `dh` with accumulate) of w / (1 + w) * mse (bcnf_head_mse_backward)."""
     B, K = h.shape
-    N.check(N.lib().bcnf_head_mse_backward(N.ptr(h), ctypes.c_int64(h.stride(0)), ctypes.c_int32(K), N.ptr(wp),
-                                           N.ptr(work), N.ptr(dvals), ctypes.c_float(weight), ctypes.c_int64(B),
-                                           ctypes.c_int32(D), N.ptr(dwp), N.ptr(dbp), N.ptr(dh),
-                                           ctypes.c_int64(dh.stride(0) if dh is not None else K),
-                                           ctypes.c_int32(int(accumulate)), N.stream_handle(h.device)),
-            "bcnf_head_mse_backward")
+    N.call("bcnf_head_mse_backward", h, h.stride(0), K, wp, work, dvals, weight, B, D, dwp, dbp, dh,
+           dh.stride(0) if dh is not None else K, accumulate, N.stream_handle(h.device))
 
 
 def launch_hybrid_finalize(vals, work, B: int, D: int, weight: float, guard):
     """vals = [nll, nll, 0] -> [(nll + w mse) / (1 + w), nll, mse] (bcnf_hybrid_finalize)."""
-    N.check(N.lib().bcnf_hybrid_finalize(N.ptr(vals), N.ptr(work), ctypes.c_int64(B), ctypes.c_int32(D),
-                                         ctypes.c_float(weight), N.ptr(guard), N.stream_handle(vals.device)),
-            "bcnf_hybrid_finalize")
+    N.call("bcnf_hybrid_finalize", vals, work, B, D, weight, guard, N.stream_handle(vals.device))
 
 
 class _HybridNLL(torch.autograd.Function):
@@ -731,7 +632,7 @@ class _HybridNLL(torch.autograd.Function):
     stack's, and (deferred reduction) the finalize of all three values."""
 
     @staticmethod
-    def forward(ctx, y, h, flat_param, wp, bp, stack: FusedStack, training: bool, defer: bool, weight: float):
+    def forward(ctx, y, h, flat_param, wp, bp, stack: StackBase, training: bool, defer: bool, weight: float):
         z, _, vals, saved = stack.launch_nll_forward(y, h, training, finalize=not defer)
         B, D = y.shape
         work = head_workspace(B, h.shape[1], D, y.device)
@@ -769,7 +670,7 @@ class _HybridNLL(torch.autograd.Function):
         return dy, dh, (dparams if need_p else None), dwp, dbp, None, None, None, None
 
 
-def stack_hybrid(stack: FusedStack, y, h, wp, bp, weight: float, training: bool, defer: bool = False):
+def stack_hybrid(stack: StackBase, y, h, wp, bp, weight: float, training: bool, defer: bool = False):
     """[loss, nll, mse] of the hybrid loss on the fused stack + head kernels. h is materialised (the head reads it), so
     neither family's feature fold applies. Without grad: finalized values (the Trainer's validation triple)."""
     y = y.contiguous()
@@ -846,7 +747,7 @@ def log_prob_of_latent(z, ldj):
 
 class _StackInverse(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, z, h, stack: FusedStack, cond_index, training: bool, want_ldj: bool = False):
+    def forward(ctx, z, h, stack: StackBase, cond_index, training: bool, want_ldj: bool = False):
         out = stack.launch_inverse(z, h, cond_index, training, want_ldj)
         if want_ldj:
             ctx.mark_non_differentiable(*out[1:])
@@ -858,13 +759,13 @@ class _StackInverse(torch.autograd.Function):
                                   "run it under torch.no_grad().")
 
 
-def _set_standalone_params(stack: FusedStack, flat, device):
+def _set_standalone_params(stack: StackBase, flat, device):
     stack.flat = flat.detach().contiguous()
     if stack.qflat is None or stack.qflat.device != device:
         stack.qflat = torch.zeros(1, dtype=torch.float32, device=device)
 
 
-def stack_forward(stack: FusedStack, y, h, training: bool, flat=None):
+def stack_forward(stack: StackBase, y, h, training: bool, flat=None):
     y = y.contiguous()
     h = h.contiguous()
     if flat is not None:
@@ -882,9 +783,9 @@ def stack_forward(stack: FusedStack, y, h, training: bool, flat=None):
     return z, ldj
 
 
-def stack_inverse(stack: FusedStack, z, h, cond_index=None, training: bool = False, flat=None,
+def stack_inverse(stack: StackBase, z, h, cond_index=None, training: bool = False, flat=None,
                   want_ldj: bool = False):
-    """want_ldj=True: (y, ldj, log_prob) -- see FusedStack.launch_inverse."""
+    """want_ldj=True: (y, ldj, log_prob) -- see StackBase.launch_inverse."""
     z = z.contiguous()
     h = h.contiguous()
     if flat is not None:

@@ -13,8 +13,6 @@ count kept on the device (as Adam(capturable=True) does), so the step is HIP-gra
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from bcnf_amd import _native as N
@@ -56,7 +54,6 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = N.lib()
         all_grads = []
         for group in self.param_groups:
             params = [p for p in group["params"] if p.grad is not None]
@@ -76,15 +73,11 @@ class FusedAdam(torch.optim.Optimizer):
                 grads = [p.grad for p in chunk]
                 numel = N.i64_array([p.numel() for p in chunk])
                 total = sum(p.numel() for p in chunk)
-                part = torch.empty(int(L.bcnf_grad_partials(total)), dtype=torch.float32, device=dev)
-                rc = L.bcnf_adam_step(len(chunk), N.ptr_array(chunk), N.ptr_array(grads),
-                                      N.ptr_array([s["exp_avg"] for s in states]),
-                                      N.ptr_array([s["exp_avg_sq"] for s in states]), numel, N.ptr(step),
-                                      ctypes.c_double(group["lr"]), ctypes.c_double(b1), ctypes.c_double(b2),
-                                      ctypes.c_double(group["eps"]), ctypes.c_double(group["weight_decay"]),
-                                      N.ptr(part), ctypes.c_int32(0 if defer_step_count else 1), N.ptr(guard),
-                                      N.stream_handle(dev))
-                N.check(rc, "bcnf_adam_step")
+                part = torch.empty(N.call_raw("bcnf_grad_partials", total), dtype=torch.float32, device=dev)
+                N.call("bcnf_adam_step", len(chunk), N.ptr_array(chunk), N.ptr_array(grads),
+                       N.ptr_array([s["exp_avg"] for s in states]), N.ptr_array([s["exp_avg_sq"] for s in states]),
+                       numel, step, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], part,
+                       not defer_step_count, guard, N.stream_handle(dev))
                 all_grads.append((chunk, grads, numel, part))
                 if defer_step_count:
                     self._pending_steps.append(step)
@@ -111,17 +104,11 @@ class FusedAdam(torch.optim.Optimizer):
                 st["step"] = step
         b1, b2 = group["betas"]
         cur, mod = cursor if cursor is not None else (None, 0)
-        L = N.lib()
-        rc = L.bcnf_adam_step_bookkeep(len(params), N.ptr_array(params), N.ptr_array([p.grad for p in params]),
-                                       N.ptr_array([s["exp_avg"] for s in states]),
-                                       N.ptr_array([s["exp_avg_sq"] for s in states]),
-                                       N.i64_array([p.numel() for p in params]), N.ptr(step),
-                                       ctypes.c_double(group["lr"]), ctypes.c_double(b1), ctypes.c_double(b2),
-                                       ctypes.c_double(group["eps"]), ctypes.c_double(group["weight_decay"]),
-                                       N.ptr(cur), ctypes.c_int64(mod), N.ptr(log[0] if log else None),
-                                       N.ptr(log[1] if log else None), N.ptr(counter), N.ptr(guard),
-                                       N.stream_handle(params[0].device))
-        N.check(rc, "bcnf_adam_step_bookkeep")
+        N.call("bcnf_adam_step_bookkeep", len(params), N.ptr_array(params), N.ptr_array([p.grad for p in params]),
+               N.ptr_array([s["exp_avg"] for s in states]), N.ptr_array([s["exp_avg_sq"] for s in states]),
+               N.i64_array([p.numel() for p in params]), step, float(group["lr"]), b1, b2, group["eps"],
+               group["weight_decay"], cur, mod, log[0] if log else None, log[1] if log else None, counter, guard,
+               N.stream_handle(params[0].device))
         self._partials = None            # no clip may follow this step
         self._partials_for = None
         return None
@@ -174,7 +161,6 @@ class FusedAdam(torch.optim.Optimizer):
         `guard`: a halted step clips nothing and advances nothing. Returns the pre-clip total norm (device)."""
         if not self._partials:
             raise RuntimeError("bcnf_amd FusedAdam: clip_grad_norm_after_step() needs a preceding step()")
-        L = N.lib()
         pending, self._pending_steps = self._pending_steps, []
         cur, mod = cursor if cursor is not None else (None, 0)
         if len(self._partials) != 1 or len(pending) > 1:   # several launches: generic path
@@ -183,18 +169,16 @@ class FusedAdam(torch.optim.Optimizer):
             norm = clip_grad_norm_(self._partials_for, max_norm)
             dev = norm.device
             for st in pending:
-                N.check(L.bcnf_advance_counters(N.ptr(st), None, 0, N.stream_handle(dev)), "bcnf_advance_counters")
+                N.call("bcnf_advance_counters", st, None, 0, N.stream_handle(dev))
             if cur is not None:
-                N.check(L.bcnf_advance_counters(None, N.ptr(cur), mod, N.stream_handle(dev)), "bcnf_advance_counters")
+                N.call("bcnf_advance_counters", None, cur, mod, N.stream_handle(dev))
             return norm
         _, grads, numel, part = self._partials[0]
         dev = grads[0].device
         norm = torch.empty((), dtype=torch.float32, device=dev)
-        rc = L.bcnf_clip_grad_norm(len(grads), N.ptr_array(grads), numel, N.ptr(part), ctypes.c_float(max_norm),
-                                   N.ptr(norm), N.ptr(pending[0] if pending else None), N.ptr(cur),
-                                   ctypes.c_int64(mod), N.ptr(log[0] if log else None), N.ptr(log[1] if log else None),
-                                   N.ptr(guard), N.stream_handle(dev))
-        N.check(rc, "bcnf_clip_grad_norm")
+        N.call("bcnf_clip_grad_norm", len(grads), N.ptr_array(grads), numel, part, max_norm, norm,
+               pending[0] if pending else None, cur, mod, log[0] if log else None, log[1] if log else None, guard,
+               N.stream_handle(dev))
         return norm
 
 
@@ -208,7 +192,6 @@ def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0):
     grads = [p.grad for p in parameters if p.grad is not None]
     if not grads:
         return torch.zeros(())
-    L = N.lib()
     dev = grads[0].device
     if len(grads) > N.MAX_TENSORS:
         # more tensors than one launch takes (a layerwise AnyGLU stack's per-layer parameters): the squared sums per
@@ -216,10 +199,9 @@ def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0):
         sq = []
         for chunk in _groups(grads):
             numel = N.i64_array([g.numel() for g in chunk])
-            part = torch.empty(int(L.bcnf_grad_partials(sum(g.numel() for g in chunk))), dtype=torch.float32,
+            part = torch.empty(N.call_raw("bcnf_grad_partials", sum(g.numel() for g in chunk)), dtype=torch.float32,
                                device=dev)
-            N.check(L.bcnf_grad_sumsq(len(chunk), N.ptr_array(chunk), numel, N.ptr(part), N.stream_handle(dev)),
-                    "bcnf_grad_sumsq")
+            N.call("bcnf_grad_sumsq", len(chunk), N.ptr_array(chunk), numel, part, N.stream_handle(dev))
             sq.append(part[:-1].sum())              # the last slot is the clip's pre-reduce scratch
         norm = torch.stack(sq).sum().sqrt()
         coef = torch.clamp(max_norm / (norm + 1e-6), max=1.0)
@@ -227,11 +209,10 @@ def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0):
         return norm
     numel = N.i64_array([g.numel() for g in grads])
     total = sum(g.numel() for g in grads)
-    part = torch.empty(int(L.bcnf_grad_partials(total)), dtype=torch.float32, device=dev)
+    part = torch.empty(N.call_raw("bcnf_grad_partials", total), dtype=torch.float32, device=dev)
     stream = N.stream_handle(dev)
-    N.check(L.bcnf_grad_sumsq(len(grads), N.ptr_array(grads), numel, N.ptr(part), stream), "bcnf_grad_sumsq")
+    N.call("bcnf_grad_sumsq", len(grads), N.ptr_array(grads), numel, part, stream)
     norm = torch.empty((), dtype=torch.float32, device=dev)
-    N.check(L.bcnf_clip_grad_norm(len(grads), N.ptr_array(grads), numel, N.ptr(part), ctypes.c_float(max_norm),
-                                  N.ptr(norm), None, None, ctypes.c_int64(0), None, None, None, stream),
-            "bcnf_clip_grad_norm")
+    N.call("bcnf_clip_grad_norm", len(grads), N.ptr_array(grads), numel, part, max_norm, norm, None, None, 0, None,
+           None, None, stream)
     return norm

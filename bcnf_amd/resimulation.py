@@ -100,13 +100,10 @@ def resimulate_device(y_hat, T: float, dt: float, data_dict: dict, parameter_ind
         fixed_d = torch.from_numpy(fixed).to(device)
         tgrid_d = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(device)
         col_arr = (ctypes.c_int32 * len(cols))(*cols)
-        L = _native.lib()
         with torch.cuda.device(device):
-            _native.check(L.bcnf_resimulate(_native.ptr(yt), 1 if yt.dtype == torch.float64 else 0, M, N, D, col_arr,
-                                            _native.ptr(fixed_d), _native.ptr(tgrid_d), steps, float(dt),
-                                            1 if break_on_impact else 0, float(rtol), float(atol), int(max_attempts),
-                                            _native.ptr(x), _native.ptr(attempts), _native.ptr(status),
-                                            _native.stream_handle(device)), "bcnf_resimulate")
+            _native.call("bcnf_resimulate", yt, yt.dtype == torch.float64, M, N, D, col_arr, fixed_d, tgrid_d, steps,
+                         float(dt), bool(break_on_impact), float(rtol), float(atol), int(max_attempts), x, attempts,
+                         status, _native.stream_handle(device))
     if return_status:
         return x, attempts, status
     return x

@@ -330,8 +330,7 @@ class TrainStep:
         if self.world == 1 or self._guard is None:
             return
         from bcnf_amd import _native as N
-        N.check(N.lib().bcnf_guard_check_global(N.ptr(self._gvals), N.ptr(self._guard),
-                                                N.stream_handle(self._gvals.device)), "bcnf_guard_check_global")
+        N.call("bcnf_guard_check_global", self._gvals, self._guard, N.stream_handle(self._gvals.device))
 
     def _update(self, vals=None, clip: bool = True, epoch_book: bool = True):
         """Adam, then clip_grad_norm_ after the step (trainer.py:273-275); the clip launch also advances the
@@ -405,11 +404,9 @@ class TrainStep:
         st = N.stream_handle(py.device)
         if self._epoch is not None:
             order, cursor = self._epoch[0], self._epoch[1]
-            N.check(N.lib().bcnf_gather_batch(N.ptr(order), N.ptr(cursor), n, N.ptr(py), cy, N.ptr(y), N.ptr(pt), ct,
-                                              N.ptr(t), st), "bcnf_gather_batch")
+            N.call("bcnf_gather_batch", order, cursor, n, py, cy, y, pt, ct, t, st)
         else:
-            N.check(N.lib().bcnf_gather_rows2(N.ptr(self._static[2]), n, N.ptr(py), cy, N.ptr(y), N.ptr(pt), ct,
-                                              N.ptr(t), st), "bcnf_gather_rows2")
+            N.call("bcnf_gather_rows2", self._static[2], n, py, cy, y, pt, ct, t, st)
         if defer:
             return y, self._unpad(t), None
         return y, self._unpad(t)

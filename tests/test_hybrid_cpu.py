@@ -91,6 +91,22 @@ def test_state_dict_and_flat_parameters(g15, name):
     assert tuple(m.prediction_head.weight.shape) == (c.cfg["D"], c.cfg["C"])
 
 
+@pytest.mark.parametrize("name", ["a", "c"])
+def test_families_are_siblings(g15, name):
+    """The small and the wide family share StackBase and nothing else: the wide stack is no FusedStack and does not
+    inherit the small family's pack-free forward switch, its table or the pending fused-Adam slot."""
+    from bcnf_amd import CondRealNVP_v2
+    from bcnf_amd.fused import FusedStack, StackBase
+    from bcnf_amd.wide import WideStack
+    assert not issubclass(WideStack, FusedStack) and not issubclass(FusedStack, WideStack)
+    st = CondRealNVP_v2.from_config(case_config(Case(g15, name).cfg)).fused
+    assert isinstance(st, StackBase)
+    small = type(st) is FusedStack
+    assert small == (name == "c")
+    for member in ("raw_table", "use_raw_forward", "pending_adam"):
+        assert hasattr(st, member) == small, member
+
+
 def test_head_abi_argument_checks():
     """Bad arguments come back as BCNF_ERR_ARG before any launch (so this runs without a GPU); the workspace size is
     positive and does not decrease in B."""

@@ -307,3 +307,50 @@ def test_wide_backward_plan_stays_inside_the_workspace(shape):
             assert crossed == {B == 35}          # the [dWf | dbf] need stops fitting below B = 35
     assert lib.bcnf_wide_backward_plan(ctypes.byref(d), 8, xp, 1, 1, 0, nb + 1, out) == N.ERR_ARG
     assert lib.bcnf_wide_backward_plan(ctypes.byref(d), 8, xp, 1, 1, 2, 2, out) == N.ERR_ARG
+
+
+def test_call_marshals_like_the_hand_wrapped_form():
+    """N.call / N.call_raw / N.query_i64(name, ...) against the real library's host-only entry points: the same values
+    as the hand-wrapped N.lib() calls for the same descriptor, with a Structure passed by reference or as a byref, a
+    bool or an int where int32_t is declared, None for a pointer and a CPU tensor as its data pointer."""
+    from bcnf_amd import _native as N
+    lib = N.lib()
+    d = N.make_desc(19, [48] * 3, 5, 80, 0.2, True)
+    small = N.make_desc(19, [16] * 7, 32, 80, 0.383, True)
+    for name, dd in (("bcnf_packed_bytes", small), ("bcnf_wide_packed_bytes", d)):
+        want = ctypes.c_int64(0)
+        assert getattr(lib, name)(ctypes.byref(dd), ctypes.byref(want)) == N.OK and want.value > 0
+        assert N.query_i64(name, dd) == N.query_i64(name, ctypes.byref(dd)) == want.value
+        assert N.query_i64(getattr(lib, name), ctypes.byref(dd)) == want.value        # the function-object form
+    want = (ctypes.c_int64 * 8)()
+    assert lib.bcnf_wide_backward_plan(ctypes.byref(d), ctypes.c_int64(35), ctypes.c_int32(68), ctypes.c_int32(1),
+                                       ctypes.c_int32(0), ctypes.c_int32(1), ctypes.c_int32(5), want) == N.OK
+    for want_dx, want_dwfb in ((True, False), (1, 0)):                  # bool and int for int32_t
+        got = (ctypes.c_int64 * 8)()
+        N.call("bcnf_wide_backward_plan", d, 35, 68, want_dx, want_dwfb, 1, 5, got)
+        assert list(got) == list(want)
+    nb = N.query_i64("bcnf_fold_raw_table_bytes", small, 90)
+    tables = [torch.zeros(nb // 4, dtype=torch.int32) for _ in range(2)]
+    assert lib.bcnf_fold_raw_table(ctypes.byref(small), ctypes.c_int32(90), N.ptr(tables[0])) == N.OK
+    assert N.call_raw("bcnf_fold_raw_table", small, 90, tables[1]) == N.OK     # a tensor goes as its data_ptr()
+    assert torch.equal(tables[0], tables[1]) and bool(tables[0].any())
+    wb = N.query_i64("bcnf_wide_workspace_bytes", d, 35, True)
+    assert wb == N.query_i64(lib.bcnf_wide_workspace_bytes, ctypes.byref(d), ctypes.c_int64(35), ctypes.c_int32(1))
+    assert wb == 4 * want[0]
+    rc, (ntr, nfr) = N.query_status("bcnf_wide_param_count", d, outs=2)
+    a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+    assert lib.bcnf_wide_param_count(ctypes.byref(d), ctypes.byref(a), ctypes.byref(b)) == N.OK == rc
+    assert (ntr, nfr) == (a.value, b.value) and ntr > 0
+
+
+def test_call_raises_what_check_raises():
+    """A non-OK status through N.call: RuntimeError naming the entry point, in check's format; call_raw returns it."""
+    from bcnf_amd import _native as N
+    d = N.make_desc(19, [16] * 7, 32, 80, 0.383, True)
+    assert N.call_raw("bcnf_packed_bytes", d, None) == N.ERR_ARG           # None -> NULL output pointer
+    with pytest.raises(RuntimeError) as via_call:
+        N.call("bcnf_packed_bytes", d, None)
+    with pytest.raises(RuntimeError) as via_check:
+        N.check(N.ERR_ARG, "bcnf_packed_bytes")
+    assert str(via_call.value) == str(via_check.value)
+    assert str(via_call.value).startswith("bcnf_amd: bcnf_packed_bytes failed: ")
