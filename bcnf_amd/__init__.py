@@ -5,8 +5,8 @@ forward / inverse / sample API and state_dict layout, with the coupling stack on
 """
 from bcnf_amd.cnf import (ActNorm, CondRealNVP_v2, ConditionalAffineCouplingLayer, ConditionalInvertibleLayer,
                           ConditionalNestedNeuralNetwork, InvertibleLayer, OrthonormalTransformation)
-from bcnf_amd.feature_network import (ConcatenateCondition, FeatureNetwork, FeatureNetworkStack,
-                                      FullyConnectedFeatureNetwork, LSTMFeatureNetwork)
+from bcnf_amd.feature_network import (ConcatenateCondition, DualDomainTransformer, FeatureNetwork, FeatureNetworkStack,
+                                      FullyConnectedFeatureNetwork, LSTMFeatureNetwork, Transformer)
 from bcnf_amd.sampling import posterior_mode
 from bcnf_amd.utils import ParameterIndexMapping, inn_nll_loss, load_config, log_prob_from_latent
 
@@ -14,6 +14,7 @@ __all__ = [
     "ActNorm", "CondRealNVP_v2", "ConditionalAffineCouplingLayer", "ConditionalInvertibleLayer",
     "ConditionalNestedNeuralNetwork", "InvertibleLayer", "OrthonormalTransformation", "ConcatenateCondition",
     "FeatureNetwork", "FeatureNetworkStack", "FullyConnectedFeatureNetwork", "LSTMFeatureNetwork",
+    "Transformer", "DualDomainTransformer",
     "ParameterIndexMapping", "inn_nll_loss", "load_config", "log_prob_from_latent",
     "posterior_mode",
 ]

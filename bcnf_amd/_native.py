@@ -43,6 +43,8 @@ EXPORTS = (
     "bcnf_guard_check_global", "bcnf_abi_version",
     "bcnf_head_work_bytes", "bcnf_head_mse_forward", "bcnf_head_mse_backward", "bcnf_hybrid_finalize",
     "bcnf_stack_inverse_logdet", "bcnf_wide_inverse_logdet",
+    "bcnf_attn_forward", "bcnf_attn_backward", "bcnf_add_layernorm_forward", "bcnf_add_layernorm_work_bytes",
+    "bcnf_add_layernorm_backward",
 )
 ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
 MAX_TENSORS = 48
@@ -206,6 +208,11 @@ def _bind(lib):
         "bcnf_head_mse_backward": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, ctypes.c_float, _i64, _i32, _vp, _vp, _vp,
                                           _i64, _i32, _vp]),
         "bcnf_hybrid_finalize": (_i32, [_vp, _vp, _i64, _i32, ctypes.c_float, _vp, _vp]),
+        "bcnf_attn_forward": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
+        "bcnf_attn_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
+        "bcnf_add_layernorm_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _vp, _vp, _vp, _vp]),
+        "bcnf_add_layernorm_work_bytes": (_i32, [_i64, _i32, _pi64]),
+        "bcnf_add_layernorm_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
         "bcnf_status_string": (ctypes.c_char_p, [_i32]),
         "bcnf_abi_version": (_i32, []),
     }

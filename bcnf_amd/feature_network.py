@@ -9,13 +9,20 @@ Restated from the reference's behaviour (src/bcnf/models/feature_network.py); th
 * LSTMFeatureNetwork           feature_network.py:148-178 — reference pools over dim 0 (the BATCH axis
   of a batch_first LSTM), which crashes for batch != seq_len. `pool_dim=0` keeps that
   behaviour bit-for-bit; `pool_dim=1` pools over time (documented fix used for trajectory_LSTM_large).
+* MultiHeadAttention / TransformerBlock / Transformer  feature_network.py:183-307 and DualDomainTransformer
+  feature_network.py:401-471 — same kwargs, submodule names and state_dict keys; on fp32 GPU tensors the Linear
+  layers run on the MFMA GEMMs over (B S, d) rows and the attention core and each residual + LayerNorm as one HIP
+  launch per direction (bcnf_amd/csrc/bcnf_attn.hip); CPU tensors and shapes outside the kernels' limits run the
+  reference's chain of torch ops. A head split that does not divide (trf_size % n_heads != 0) raises on forward.
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 from typing import Any, Type
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -251,6 +258,246 @@ class LSTMFeatureNetwork(FeatureNetwork):
         return x.max(dim=self.pool_dim).values
 
 
+ATTN_MAX_SEQ = 64          # bcnf_attn_*: S <= 64, head_dim <= 64 (include/bcnf_amd.h)
+ATTN_MAX_HEAD_DIM = 64
+ADD_LN_MAX_D = 1024        # bcnf_add_layernorm_*: d <= 1024
+_LN_WORK_FLOATS: dict = {}  # (rows, d) -> floats of the backward's partials (bcnf_add_layernorm_work_bytes)
+
+
+class _AttnFn(torch.autograd.Function):
+    """softmax(q k^T / sqrt(hd)) v per (sample, head) on the (B S, heads hd) rows of the q / k / v Linear layers, in
+    ONE launch each way (bcnf_attn_forward / bcnf_attn_backward): no head transposes, no score or probability tensor;
+    the forward keeps the (B, heads, S) log-sum-exp."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, batch, seq, heads, hd):
+        from bcnf_amd import _native as N
+        out = torch.empty_like(q)
+        lse = torch.empty((batch, heads, seq), dtype=torch.float32, device=q.device)
+        N.call("bcnf_attn_forward", q, k, v, batch, seq, heads, hd, q.shape[1], out, lse, N.stream_handle(q.device))
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.dims = (batch, seq, heads, hd)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from bcnf_amd import _native as N
+        q, k, v, out, lse = ctx.saved_tensors
+        batch, seq, heads, hd = ctx.dims
+        dout = dout.contiguous()
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        N.call("bcnf_attn_backward", q, k, v, out, lse, dout, batch, seq, heads, hd, q.shape[1], dq, dk, dv,
+               N.stream_handle(q.device))
+        return dq, dk, dv, None, None, None, None
+
+
+class _AddLayerNormFn(torch.autograd.Function):
+    """y = LayerNorm(x + r) in ONE launch (bcnf_add_layernorm_forward); the backward (one launch, plus the fixed-order
+    reduce of the gamma / beta partials) returns the one dx = dr for both inputs."""
+
+    @staticmethod
+    def forward(ctx, x, r, gamma, beta, eps):
+        from bcnf_amd import _native as N
+        rows, d = x.shape
+        y = torch.empty_like(x)
+        stats = torch.empty((2, rows), dtype=torch.float32, device=x.device)       # mean | rstd
+        N.call("bcnf_add_layernorm_forward", x, r, gamma, beta, rows, d, float(eps), y, stats[0], stats[1],
+               N.stream_handle(x.device))
+        ctx.save_for_backward(x, r, gamma, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from bcnf_amd import _native as N
+        x, r, gamma, stats = ctx.saved_tensors
+        rows, d = x.shape
+        dy = dy.contiguous()
+        need_x, need_r, need_g, need_b = ctx.needs_input_grad[:4]
+        dx = torch.empty_like(x) if (need_x or need_r) else None
+        dg = db = work = None
+        if need_g or need_b:
+            wf = _LN_WORK_FLOATS.get((rows, d))
+            if wf is None:
+                wf = _LN_WORK_FLOATS[(rows, d)] = max(N.query_i64("bcnf_add_layernorm_work_bytes", rows, d) // 4, 1)
+            dg, db = torch.empty((2, d), dtype=torch.float32, device=x.device).unbind(0)
+            work = torch.empty(wf, dtype=torch.float32, device=x.device)
+        N.call("bcnf_add_layernorm_backward", x, r, gamma, stats[0], stats[1], dy, rows, d, dx,
+               dg if need_g else None, db if need_b else None, work, N.stream_handle(x.device))
+        return (dx if need_x else None), (dx if need_r else None), (dg if need_g else None), \
+            (db if need_b else None), None
+
+
+def _on_kernels(x: torch.Tensor, *params: torch.Tensor) -> bool:
+    return x.is_cuda and x.dtype == torch.float32 and all(p is None or p.dtype == torch.float32 for p in params)
+
+
+def _rows_linear(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
+    """lin(x) for x (..., k): fp32 GPU tensors go through HIPLinear as (rows, k); the rest is torch's linear."""
+    if x.dim() > 2 and _on_kernels(x, lin.weight):
+        return lin(x.reshape(-1, x.shape[-1])).view(*x.shape[:-1], lin.out_features)
+    return lin(x)
+
+
+class MultiHeadAttention(nn.Module):
+    """feature_network.py:183-229. fp32 GPU tensors with S <= 64 and head_dim <= 64: the Linear layers on the MFMA GEMMs
+    over (B S, d) rows and the attention core in one launch (_AttnFn); everything else, and `fused = False`, runs the
+    reference's chain of torch ops."""
+
+    fused = True        # False: the attention core on torch ops (fallback tests, tools/transformer_feature_ab.py)
+
+    def __init__(self, d_model: int, n_heads: int) -> None:
+        super().__init__()
+        self.d_model = d_model
+        self.n_heads = n_heads
+        self.head_dim = d_model // n_heads
+        self.q_linear = HIPLinear(d_model, d_model)
+        self.k_linear = HIPLinear(d_model, d_model)
+        self.v_linear = HIPLinear(d_model, d_model)
+        self.fc_out = HIPLinear(d_model, d_model)
+
+    def forward(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, mask=None) -> torch.Tensor:
+        if self.d_model % self.n_heads != 0:
+            # the reference's view(B, -1, n_heads, head_dim) fails here (or, where it happens to fit, silently mixes
+            # time steps into heads): t_PTRF_small (46 / 4), t_DPTRF_medium (70 / 8)
+            raise RuntimeError(f"bcnf_amd: MultiHeadAttention cannot split d_model = trf_size = {self.d_model} into "
+                               f"n_heads = {self.n_heads} heads ({self.d_model} % {self.n_heads} != 0)")
+        batch = query.size(0)
+        q = _rows_linear(self.q_linear, query)
+        k = _rows_linear(self.k_linear, key)
+        v = _rows_linear(self.v_linear, value)
+        seq = q.shape[1] if q.dim() == 3 else -1
+        if (self.fused and mask is None and q.dim() == 3 and q.shape == k.shape == v.shape and _on_kernels(q)
+                and 1 <= seq <= ATTN_MAX_SEQ and self.head_dim <= ATTN_MAX_HEAD_DIM and batch > 0):
+            rows = batch * seq
+            out = _AttnFn.apply(q.reshape(rows, self.d_model), k.reshape(rows, self.d_model),
+                                v.reshape(rows, self.d_model), batch, seq, self.n_heads, self.head_dim)
+            out = out.view(batch, seq, self.d_model)
+        else:
+            q = q.view(batch, -1, self.n_heads, self.head_dim).transpose(1, 2)
+            k = k.view(batch, -1, self.n_heads, self.head_dim).transpose(1, 2)
+            v = v.view(batch, -1, self.n_heads, self.head_dim).transpose(1, 2)
+            scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(self.head_dim)
+            if mask is not None:
+                scores = scores.masked_fill(mask == 0, -1e9)
+            out = torch.matmul(torch.softmax(scores, dim=-1), v)
+            out = out.transpose(1, 2).contiguous().view(batch, -1, self.d_model)
+        return _rows_linear(self.fc_out, out)
+
+
+class TransformerBlock(nn.Module):
+    """feature_network.py:232-260, post-norm: norm1(x + drop(attn(x))), norm2(x + drop(ffn(x))) with ONE Dropout module.
+    fp32 GPU tensors: each residual + LayerNorm in one launch (_AddLayerNormFn, d <= 1024) and the FFN's Linear + GELU
+    in one (_LinearGeluFn, p = 0); `fused = False` keeps the two norms on torch ops."""
+
+    fused = True        # False: x + r and LayerNorm on torch ops
+
+    def __init__(self, d_model: int, n_heads: int, ff_size: int, dropout: float = 0.1) -> None:
+        super().__init__()
+        self.attention = MultiHeadAttention(d_model, n_heads)
+        self.norm1 = nn.LayerNorm(d_model)
+        self.norm2 = nn.LayerNorm(d_model)
+        self.ffn = nn.Sequential(HIPLinear(d_model, ff_size), nn.GELU(), HIPLinear(ff_size, d_model))
+        self.dropout = nn.Dropout(dropout)
+
+    def _add_norm(self, norm: nn.LayerNorm, x: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+        d = x.shape[-1]
+        if (self.fused and norm.elementwise_affine and norm.bias is not None and d <= ADD_LN_MAX_D
+                and x.shape == r.shape and x.numel() > 0 and _on_kernels(x, norm.weight) and r.dtype == x.dtype):
+            y = _AddLayerNormFn.apply(x.reshape(-1, d).contiguous(), r.reshape(-1, d).contiguous(), norm.weight,
+                                      norm.bias, norm.eps)
+            return y.view(x.shape)
+        return norm(x + r)
+
+    def _ffn(self, x: torch.Tensor) -> torch.Tensor:
+        lin0, lin1 = self.ffn[0], self.ffn[2]
+        if x.dim() == 3 and x.numel() > 0 and _on_kernels(x, lin0.weight):
+            rows = x.reshape(-1, x.shape[-1]).contiguous()
+            need_g = torch.is_grad_enabled() and (rows.requires_grad or lin0.weight.requires_grad or
+                                                  (lin0.bias is not None and lin0.bias.requires_grad))
+            a = _LinearGeluFn.apply(rows, lin0.weight, lin0.bias, 0.0, None, 0, need_g)
+            return lin1(a).view(*x.shape[:-1], lin1.out_features)
+        return self.ffn(x)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = self._add_norm(self.norm1, x, self.dropout(self.attention(x, x, x)))
+        return self._add_norm(self.norm2, x, self.dropout(self._ffn(x)))
+
+
+class Transformer(FeatureNetwork):
+    """feature_network.py:263-307: features Linear, ONE Dropout(dropout) applied after it and again after the last
+    block to the whole (B, S, d) tensor, positional table added in between, then `output` of the first token."""
+
+    def __init__(self, input_size: int, trf_size: int, n_heads: int, ff_size: int, n_blocks: int, output_size: int,
+                 dropout: float = 0.5, trf_dropout: float = 0.1, add_positional_embeddings: bool = False) -> None:
+        super().__init__()
+        self.input_size = input_size
+        self.output_size = output_size
+        self.add_positional_embeddings = add_positional_embeddings
+        self.trf_size = trf_size
+        self.features = HIPLinear(input_size, trf_size)
+        self.layers = nn.ModuleList([TransformerBlock(trf_size, n_heads, ff_size, trf_dropout)
+                                     for _ in range(n_blocks)])
+        self.output = HIPLinear(trf_size, output_size)
+        self.dropout = nn.Dropout(dropout)
+        self._tables: dict = {}        # (S, device) -> table; a plain cache, not a buffer: no state_dict key
+
+    def positional_table(self, seq_len: int, device) -> torch.Tensor:
+        """The reference's (S, trf_size) table (feature_network.py:289-295): only columns j < input_size are filled,
+        sin for even j and cos for odd j of i / 10000 ** (2 j / input_size), evaluated in float64 and stored as
+        float32. Built once per (S, device)."""
+        key = (int(seq_len), str(device))
+        table = self._tables.get(key)
+        if table is None:
+            host = torch.zeros(seq_len, self.trf_size)
+            for i in range(seq_len):
+                for j in range(self.input_size):
+                    angle = i / 10000 ** (2 * j / self.input_size)
+                    host[i, j] = np.sin(angle) if j % 2 == 0 else np.cos(angle)
+            table = self._tables[key] = host.to(device)
+        return table
+
+    def first_token(self, x: torch.Tensor) -> torch.Tensor:
+        """Everything before `output`: the dropped-out first token (B, trf_size) of the last block."""
+        x = self.dropout(_rows_linear(self.features, x))
+        if self.add_positional_embeddings:
+            x = x + self.positional_table(x.size(1), x.device)
+        for layer in self.layers:
+            x = layer(x)
+        return self.dropout(x)[:, 0, :]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.output(self.first_token(x))
+
+
+class DualDomainTransformer(FeatureNetwork):
+    """feature_network.py:401-471: a Transformer on x, one on cat(rfft(x, dim=1).real, .imag) (S // 2 + 1 bins of
+    2 input_size values), and a FullyConnectedFeatureNetwork on their concatenated (B, 2 trf_size) outputs."""
+
+    def __init__(self, input_size: int, trf_size: int, n_heads: int, ff_size: int, n_blocks: int, fc_sizes: list[int],
+                 fc_dropout: float = 0.5, trf_dropout: float = 0.1, dropout: float = 0.5,
+                 add_positional_embeddings: bool = False) -> None:
+        super().__init__()
+        self.input_size = input_size
+        self.output_size = fc_sizes[-1]
+        self.add_positional_embeddings = add_positional_embeddings
+        kwargs = dict(trf_size=trf_size, n_heads=n_heads, ff_size=ff_size, n_blocks=n_blocks, output_size=trf_size,
+                      dropout=dropout, trf_dropout=trf_dropout, add_positional_embeddings=add_positional_embeddings)
+        self.time_transformer = Transformer(input_size=input_size, **kwargs)
+        self.frequency_transformer = Transformer(input_size=input_size * 2, **kwargs)
+        self.fc_sizes = [trf_size * 2] + list(fc_sizes)
+        self.fc = FullyConnectedFeatureNetwork(sizes=self.fc_sizes, dropout=fc_dropout)
+
+    def combined(self, x: torch.Tensor) -> torch.Tensor:
+        """The input of `fc`: (B, 2 trf_size) = [time branch | frequency branch]."""
+        x_out = self.time_transformer(x)
+        freq = torch.fft.rfft(x, dim=1)
+        x_frequency_out = self.frequency_transformer(torch.cat([freq.real, freq.imag], dim=-1))
+        return torch.cat([x_out, x_frequency_out], dim=1)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fc(self.combined(x))
+
+
 class FeatureNetworkStack(FeatureNetwork):
     def __init__(self, feature_networks: list[nn.Module | None] | None = None) -> None:
         super().__init__()
@@ -279,5 +526,7 @@ class FeatureNetworkStack(FeatureNetwork):
 FEATURE_NETWORKS: dict[str, Any] = {
     "FullyConnected": FullyConnectedFeatureNetwork,
     "LSTM": LSTMFeatureNetwork,
+    "Transformer": Transformer,
+    "DualDomainTransformer": DualDomainTransformer,
     "ConcatenateCondition": ConcatenateCondition,
 }

@@ -58,6 +58,48 @@ from bcnf_amd.utils import inn_nll_loss
 GUARD_CHECK, GUARD_DIVERGED, GUARD_HALTED, GUARD_CHECK_GLOBAL, GUARD_WORDS = 0, 1, 2, 3, 4    # include/bcnf_amd.h
 
 
+class _PackedParameters:
+    """The optimizer's view of a feature network with more parameter tensors than one Adam / clip launch takes
+    (N.MAX_TENSORS; a Transformer has 16 per block): the member parameters become views of ONE flat parameter, and
+    after each backward their gradients are gathered into ONE flat gradient (a torch.cat, capturable) of which each
+    member's .grad is then a view -- so the update, the clip after the step, the logged values and the divergence guard
+    keep their single-launch form, and p.grad shows the clipped gradient as it does for every other model."""
+
+    def __init__(self, members):
+        self.members = list(members)
+        dev = self.members[0].device
+        flat = torch.empty(sum(p.numel() for p in self.members), dtype=torch.float32, device=dev)
+        self.slices = []
+        off = 0
+        with torch.no_grad():
+            for p in self.members:
+                n = p.numel()
+                flat[off:off + n].copy_(p.detach().reshape(-1))
+                p.data = flat[off:off + n].view(p.shape)
+                self.slices.append((off, off + n))
+                off += n
+        self.param = torch.nn.Parameter(flat)
+        self.flat_grad = torch.zeros_like(flat)
+
+    def intact(self) -> bool:
+        """The members still are the views (Module.to / .float() after the TrainStep was built replaces them)."""
+        base = self.param.data_ptr()
+        return all(p.data_ptr() == base + 4 * lo for p, (lo, _) in zip(self.members, self.slices))
+
+    def clear(self):
+        for p in self.members:
+            p.grad = None
+
+    def gather(self):
+        grads = [p.grad for p in self.members]
+        if any(g is None for g in grads):
+            raise RuntimeError("bcnf_amd TrainStep: a feature-network parameter received no gradient")
+        torch.cat([g.reshape(-1) for g in grads], out=self.flat_grad)
+        for p, (lo, hi) in zip(self.members, self.slices):
+            p.grad = self.flat_grad[lo:hi].view(p.shape)
+        self.param.grad = self.flat_grad
+
+
 class TrainStep:
     def __init__(self, model, lr: float = 2e-4, hybrid_weight: float = 0.0, capture: bool = True,
                  max_norm: float = 1.0, process_group=None, overlap_ranges: int = 0):
@@ -69,6 +111,15 @@ class TrainStep:
         self.model = model
         self.params = [p for p in model.parameters() if p.requires_grad] if self.layerwise \
             else model.flat_parameters()
+        self._packed = None
+        from bcnf_amd import _native as N
+        if not self.layerwise and len(self.params) > N.MAX_TENSORS and model.n_conditions > 0:
+            members = {id(p) for p in model.feature_network_stack.parameters()}
+            feature = [p for p in self.params if id(p) in members]
+            if feature and all(p.is_cuda and p.dtype == torch.float32 for p in feature):
+                self._packed = _PackedParameters(feature)
+                self.params = [p for p in self.params if id(p) not in members]
+                self.params.insert(1, self._packed.param)
         self.hybrid_weight = float(hybrid_weight)
         self.max_norm = max_norm
         self.capture = capture and not self.layerwise
@@ -124,8 +175,16 @@ class TrainStep:
 
     # ------------------------------------------------------------------ step pieces
     def _forward_backward(self, y, traj, gather=None, adam=None):
+        if self._packed is not None:
+            if not self._packed.intact():
+                raise RuntimeError("bcnf_amd TrainStep: the model's feature-network parameters were replaced (moved or "
+                                   "cast) after this TrainStep packed them; build a new TrainStep")
+            self._packed.clear()
         with self._stack_hooks(), self._side_overlap():
-            return self._forward_backward_body(y, traj, gather, adam)
+            vals = self._forward_backward_body(y, traj, gather, adam)
+        if self._packed is not None:
+            self._packed.gather()
+        return vals
 
     @contextlib.contextmanager
     def _side_overlap(self):

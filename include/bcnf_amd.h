@@ -476,6 +476,32 @@ int bcnf_head_mse_backward(const float* x, int64_t ldx, int32_t in_features, con
 int bcnf_hybrid_finalize(float* loss_vals, const void* work, int64_t batch, int32_t out_features, float weight,
                          int32_t* guard, void* stream);
 
+/* ---- Transformer feature networks (feature_network.py:183-307: MultiHeadAttention, TransformerBlock) ---------------
+ * The two pieces of a block that are not a Linear layer. fp32, stream-ordered, stateless; every sum runs in a fixed
+ * order (same inputs, same bits). A shape outside the stated limits returns BCNF_ERR_ARG and launches nothing.
+ *
+ * Attention core: out = softmax(q k^T / sqrt(head_dim)) v per (sample, head), no mask. q, k, v, out (and dout, dq, dk,
+ * dv) are (B * S) rows of n_heads * head_dim floats, `ld` >= n_heads * head_dim floats apart; head h is columns
+ * h * head_dim .. h * head_dim + head_dim - 1 (the head split and concatenation are index arithmetic; columns past
+ * n_heads * head_dim of a row are neither read nor written). 1 <= S <= 64, 1 <= head_dim <= 64. lse is
+ * (B, n_heads, S): the log-sum-exp of each score row, which the backward recomputes the probabilities from. */
+int bcnf_attn_forward(const float* q, const float* k, const float* v, int64_t batch, int32_t seq_len, int32_t n_heads,
+                      int32_t head_dim, int64_t ld, float* out, float* lse, void* stream);
+int bcnf_attn_backward(const float* q, const float* k, const float* v, const float* out, const float* lse,
+                       const float* dout, int64_t batch, int32_t seq_len, int32_t n_heads, int32_t head_dim,
+                       int64_t ld, float* dq, float* dk, float* dv, void* stream);
+/* Residual + LayerNorm: y = LayerNorm(x + r) over rows of d contiguous floats (biased variance, eps inside the square
+ * root; gamma (d), beta (d, nullable)); mean / rstd (rows) are saved for the backward. 1 <= d <= 1024.
+ * backward: dx (rows x d, nullable) is the gradient of x AND of r; dgamma / dbeta (d, nullable) are summed per
+ * workgroup into `work` (caller-owned, bcnf_add_layernorm_work_bytes(rows, d) bytes; may be NULL when neither is
+ * wanted) and reduced over the workgroups, in order, by a second launch. */
+int bcnf_add_layernorm_forward(const float* x, const float* r, const float* gamma, const float* beta, int64_t rows,
+                               int32_t d, float eps, float* y, float* mean, float* rstd, void* stream);
+int bcnf_add_layernorm_work_bytes(int64_t rows, int32_t d, int64_t* bytes);
+int bcnf_add_layernorm_backward(const float* x, const float* r, const float* gamma, const float* mean,
+                                const float* rstd, const float* dy, int64_t rows, int32_t d, float* dx, float* dgamma,
+                                float* dbeta, void* work, void* stream);
+
 /* ---- Calibration (eval/calibration.py:20-48, compute_y_hat_ranks) -----------------------------------------------
  * counts[i * dim + d] += #{ s < n_draws : y_hat[(s * n_rows + i) * dim + d] < y[i * dim + d] } for the (n_draws, n_rows,
  * dim) draws of sample(outer=True); counts is uint32 and accumulates, so draws can be fed in chunks. */
