@@ -373,9 +373,8 @@ int attn_fwd_launch(const float* q, const float* k, const float* v, long long B,
                     float* out, float* lse, hipStream_t st) {
   constexpr int SLOTS = AWAVES * (64 / SB);
   const long long items = B * heads;
-  hipLaunchKernelGGL((k_attn_fwd<SB, HDB>), dim3((unsigned)((items + SLOTS - 1) / SLOTS)), dim3(AWG), 0, st, q, k, v,
-                     items, S, heads, hd, ld, 1.f / sqrtf((float)hd), out, lse);
-  return bcnf_rt::launched();
+  return bcnf_rt::launch<k_attn_fwd<SB, HDB>>(dim3((unsigned)((items + SLOTS - 1) / SLOTS)), dim3(AWG), 0, st, q, k, v,
+                                              items, S, heads, hd, ld, 1.f / sqrtf((float)hd), out, lse);
 }
 
 template <int SB, int HDB>
@@ -384,9 +383,9 @@ int attn_bwd_launch(const float* q, const float* k, const float* v, const float*
                     float* dv, hipStream_t st) {
   constexpr int SLOTS = AWAVES * (64 / SB);
   const long long items = B * heads;
-  hipLaunchKernelGGL((k_attn_bwd<SB, HDB>), dim3((unsigned)((items + SLOTS - 1) / SLOTS)), dim3(AWG), 0, st, q, k, v,
-                     out, lse, dout, items, S, heads, hd, ld, 1.f / sqrtf((float)hd), dq, dk, dv);
-  return bcnf_rt::launched();
+  return bcnf_rt::launch<k_attn_bwd<SB, HDB>>(dim3((unsigned)((items + SLOTS - 1) / SLOTS)), dim3(AWG), 0, st, q, k, v,
+                                              out, lse, dout, items, S, heads, hd, ld, 1.f / sqrtf((float)hd), dq, dk,
+                                              dv);
 }
 
 // (S <= 32 | S <= 64) x head_dim bucket (8, 16, 32, 64): the register arrays of a lane have these compile-time sizes
@@ -404,15 +403,13 @@ int attn_bwd_launch(const float* q, const float* k, const float* v, const float*
     return FN<64, 64>(__VA_ARGS__);                                  \
   } while (0)
 
-// elements per lane of a LayerNorm row: ceil(d / 64) rounded up to a power of two
-#define LN_DISPATCH(K, GRID, ST, ...)                                                        \
-  do {                                                                                       \
-    if (d <= 64) hipLaunchKernelGGL(K<1>, GRID, dim3(AWG), 0, ST, __VA_ARGS__);              \
-    else if (d <= 128) hipLaunchKernelGGL(K<2>, GRID, dim3(AWG), 0, ST, __VA_ARGS__);        \
-    else if (d <= 256) hipLaunchKernelGGL(K<4>, GRID, dim3(AWG), 0, ST, __VA_ARGS__);        \
-    else if (d <= 512) hipLaunchKernelGGL(K<8>, GRID, dim3(AWG), 0, ST, __VA_ARGS__);        \
-    else hipLaunchKernelGGL(K<16>, GRID, dim3(AWG), 0, ST, __VA_ARGS__);                     \
-  } while (0)
+// elements per lane of a LayerNorm row: ceil(d / 64) rounded up to a power of two; the value is the launch's status
+#define LN_DISPATCH(K, GRID, ST, ...)                                            \
+  (d <= 64    ? bcnf_rt::launch<K<1>>(GRID, dim3(AWG), 0, ST, __VA_ARGS__)       \
+   : d <= 128 ? bcnf_rt::launch<K<2>>(GRID, dim3(AWG), 0, ST, __VA_ARGS__)       \
+   : d <= 256 ? bcnf_rt::launch<K<4>>(GRID, dim3(AWG), 0, ST, __VA_ARGS__)       \
+   : d <= 512 ? bcnf_rt::launch<K<8>>(GRID, dim3(AWG), 0, ST, __VA_ARGS__)       \
+              : bcnf_rt::launch<K<16>>(GRID, dim3(AWG), 0, ST, __VA_ARGS__))
 
 }  // namespace
 
@@ -438,8 +435,7 @@ int bcnf_add_layernorm_forward(const float* x, const float* r, const float* gamm
   LnPlan P;
   if (!x || !r || !gamma || !y || !mean || !rstd || !(eps >= 0.f) || !ln_plan(rows, d, &P)) return BCNF_ERR_ARG;
   const dim3 grid((unsigned)((rows + AWAVES - 1) / AWAVES));
-  LN_DISPATCH(k_add_ln_fwd, grid, (hipStream_t)stream, x, r, gamma, beta, (long long)rows, d, eps, y, mean, rstd);
-  return bcnf_rt::launched();
+  return LN_DISPATCH(k_add_ln_fwd, grid, (hipStream_t)stream, x, r, gamma, beta, (long long)rows, d, eps, y, mean, rstd);
 }
 
 int bcnf_add_layernorm_work_bytes(int64_t rows, int32_t d, int64_t* bytes) {
@@ -458,15 +454,11 @@ int bcnf_add_layernorm_backward(const float* x, const float* r, const float* gam
   if (params && !work) return BCNF_ERR_ARG;
   if (!dx && !params) return BCNF_OK;
   hipStream_t st = (hipStream_t)stream;
-  LN_DISPATCH(k_add_ln_bwd, dim3((unsigned)P.nwg), st, x, r, gamma, mean, rstd, dy, (long long)rows, d, P.rpw, dx,
-              params ? static_cast<float*>(work) : nullptr);
-  if (const int rc = bcnf_rt::launched()) return rc;
-  if (params) {
-    hipLaunchKernelGGL(k_add_ln_reduce, dim3((unsigned)((2 * d + LN_RC - 1) / LN_RC)), dim3(AWG), 0, st,
-                       static_cast<const float*>(work), P.nwg, d, dgamma, dbeta);
-    if (const int rc = bcnf_rt::launched()) return rc;
-  }
-  return BCNF_OK;
+  const int rc = LN_DISPATCH(k_add_ln_bwd, dim3((unsigned)P.nwg), st, x, r, gamma, mean, rstd, dy, (long long)rows, d,
+                             P.rpw, dx, params ? static_cast<float*>(work) : nullptr);
+  if (rc || !params) return rc;
+  return bcnf_rt::launch<k_add_ln_reduce>(dim3((unsigned)((2 * d + LN_RC - 1) / LN_RC)), dim3(AWG), 0, st,
+                                          static_cast<const float*>(work), P.nwg, d, dgamma, dbeta);
 }
 
 }  // extern "C"

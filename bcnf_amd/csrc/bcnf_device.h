@@ -9,6 +9,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <mutex>
+#include <utility>
+
 #include "../../include/bcnf_amd.h"
 
 #define BCNF_WG 256
@@ -21,7 +25,43 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 // keeps no error state between calls.
 namespace bcnf_rt {
 inline int hip_status(hipError_t e) { return e == hipSuccess ? 0 : BCNF_ERR_HIP_BASE + (int)e; }
-inline int launched() { return hip_status(hipGetLastError()); }
+
+constexpr size_t LDS_MAX = 160 * 1024;   // the LDS of one gfx950 workgroup
+
+// Dynamic LDS of a launch: the launch's own bytes and the limit to ask the runtime for when the kernel's has to grow
+// (a kernel whose requests vary names its ceiling, so that its first launch is the only one that asks).
+struct Lds {
+  size_t bytes, request;
+  Lds(size_t b) : bytes(b), request(b) {}
+  Lds(size_t b, size_t ceiling) : bytes(b), request(ceiling > b ? ceiling : b) {}
+};
+
+// The one way a kernel of the library is launched: launch<kernel>(grid, block, lds, stream, args...) -> status.
+// More than LDS_MAX is BCNF_ERR_UNSUPPORTED. A kernel with dynamic LDS has its hipFuncAttributeMaxDynamicSharedMemorySize
+// raised to lds.request when that exceeds what the kernel was granted before in this process (grow-only; a failure
+// is the status returned, and nothing is launched). The granted size is a static of this instantiation -- one per
+// kernel, no table to fill up -- read without a lock; growing takes the instantiation's mutex. So once a kernel has
+// run eagerly at some size, no launch at that size or below calls hipFuncSetAttribute, which a stream capture
+// relies on. lds.bytes == 0 never touches the attribute.
+template <auto Kernel, typename... Args>
+int launch(dim3 grid, dim3 block, Lds lds, hipStream_t stream, Args&&... args) {
+  if (lds.bytes > LDS_MAX) return BCNF_ERR_UNSUPPORTED;
+  if (lds.bytes > 0) {
+    static std::atomic<size_t> granted{0};
+    static std::mutex grow;
+    if (lds.request > granted.load(std::memory_order_acquire)) {
+      std::lock_guard<std::mutex> lk(grow);
+      if (lds.request > granted.load(std::memory_order_relaxed)) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds.request);
+        if (e != hipSuccess) return hip_status(e);
+        granted.store(lds.request, std::memory_order_release);
+      }
+    }
+  }
+  Kernel<<<grid, block, lds.bytes, stream>>>(std::forward<Args>(args)...);
+  return hip_status(hipGetLastError());
+}
 }  // namespace bcnf_rt
 
 // dst0[r] = src0[idx[r]] (cols0 floats), dst1[r] = src1[idx[r]] (cols1 floats), one launch for both;

@@ -42,8 +42,7 @@ int bcnf_rank_count(const float* y_hat, const float* y, int64_t n_draws, int64_t
   const long long ND = n_rows * (long long)dim;
   dim3 grid((unsigned)((ND + EWG - 1) / EWG), (unsigned)((n_draws + S_PER_WG - 1) / S_PER_WG));
   if (grid.y > 65535) return BCNF_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(k_rank_count, grid, dim3(EWG), 0, (hipStream_t)stream, y_hat, y, (long long)n_draws, ND, counts);
-  return bcnf_rt::launched();
+  return bcnf_rt::launch<k_rank_count>(grid, dim3(EWG), 0, (hipStream_t)stream, y_hat, y, (long long)n_draws, ND, counts);
 }
 
 }  // extern "C"

@@ -7,6 +7,8 @@
 
 namespace {
 
+using bcnf_rt::launch;
+
 constexpr int HWG = 256;          // forward / dx / finalize workgroup (4 waves)
 constexpr int HEAD_SPLITS = 64;   // most batch splits of the dW / dbias partials
 constexpr int HEAD_KW = 64;       // x columns per dW wave
@@ -295,13 +297,10 @@ int bcnf_head_mse_forward(const float* x, int64_t ldx, int32_t K, const float* W
   float* ws = static_cast<float*>(work);
   const int vecx = (ldx % 4 == 0 && aligned16(x)) ? 1 : 0, vecw = (K % 4 == 0 && aligned16(W)) ? 1 : 0;
   const dim3 grid((unsigned)P.n_mse);
-  if (D <= 16)
-    hipLaunchKernelGGL(k_head_fwd<1>, grid, dim3(HWG), 0, (hipStream_t)stream, x, (long long)ldx, K, W, bias, y,
-                       (long long)B, D, ws + P.r_off, ws + P.mse_off, vecx, vecw);
-  else
-    hipLaunchKernelGGL(k_head_fwd<2>, grid, dim3(HWG), 0, (hipStream_t)stream, x, (long long)ldx, K, W, bias, y,
-                       (long long)B, D, ws + P.r_off, ws + P.mse_off, vecx, vecw);
-  return bcnf_rt::launched();
+  return D <= 16 ? launch<k_head_fwd<1>>(grid, dim3(HWG), 0, (hipStream_t)stream, x, (long long)ldx, K, W, bias, y,
+                                         (long long)B, D, ws + P.r_off, ws + P.mse_off, vecx, vecw)
+                 : launch<k_head_fwd<2>>(grid, dim3(HWG), 0, (hipStream_t)stream, x, (long long)ldx, K, W, bias, y,
+                                         (long long)B, D, ws + P.r_off, ws + P.mse_off, vecx, vecw);
 }
 
 int bcnf_head_mse_backward(const float* x, int64_t ldx, int32_t K, const float* W, void* work, const float* dloss,
@@ -321,28 +320,23 @@ int bcnf_head_mse_backward(const float* x, int64_t ldx, int32_t K, const float* 
     if (gy > 65535) gy = 65535;
     const dim3 grid((unsigned)P.n_mse, (unsigned)gy);
     const int vecd = (ldd % 4 == 0 && aligned16(dx)) ? 1 : 0;
-    if (D <= 16)
-      hipLaunchKernelGGL(k_head_dx<1>, grid, dim3(HWG), 0, st, W, K, ws + P.r_off, dloss, wfrac, (long long)B, D, dx,
-                         (long long)ldd, accumulate_dx, vecd);
-    else
-      hipLaunchKernelGGL(k_head_dx<2>, grid, dim3(HWG), 0, st, W, K, ws + P.r_off, dloss, wfrac, (long long)B, D, dx,
-                         (long long)ldd, accumulate_dx, vecd);
-    if (const int rc = bcnf_rt::launched()) return rc;
+    const int rc = D <= 16 ? launch<k_head_dx<1>>(grid, dim3(HWG), 0, st, W, K, ws + P.r_off, dloss, wfrac, (long long)B,
+                                                  D, dx, (long long)ldd, accumulate_dx, vecd)
+                           : launch<k_head_dx<2>>(grid, dim3(HWG), 0, st, W, K, ws + P.r_off, dloss, wfrac, (long long)B,
+                                                  D, dx, (long long)ldd, accumulate_dx, vecd);
+    if (rc) return rc;
   }
   if (dW || dbias) {
     const int vecx = (ldx % 4 == 0 && aligned16(x)) ? 1 : 0;
     const dim3 grid((unsigned)P.kgroups, (unsigned)P.splits);
-    if (D <= 16)
-      hipLaunchKernelGGL(k_head_dw<1>, grid, dim3(64), 0, st, x, (long long)ldx, K, ws + P.r_off, dloss, wfrac,
-                         (long long)B, D, P.rps, P.Kp, ws + P.dw_off, ws + P.db_off, vecx);
-    else
-      hipLaunchKernelGGL(k_head_dw<2>, grid, dim3(64), 0, st, x, (long long)ldx, K, ws + P.r_off, dloss, wfrac,
-                         (long long)B, D, P.rps, P.Kp, ws + P.dw_off, ws + P.db_off, vecx);
-    if (const int rc = bcnf_rt::launched()) return rc;
+    const int rc = D <= 16 ? launch<k_head_dw<1>>(grid, dim3(64), 0, st, x, (long long)ldx, K, ws + P.r_off, dloss, wfrac,
+                                                  (long long)B, D, P.rps, P.Kp, ws + P.dw_off, ws + P.db_off, vecx)
+                           : launch<k_head_dw<2>>(grid, dim3(64), 0, st, x, (long long)ldx, K, ws + P.r_off, dloss, wfrac,
+                                                  (long long)B, D, P.rps, P.Kp, ws + P.dw_off, ws + P.db_off, vecx);
+    if (rc) return rc;
     const long long n = (long long)D * K + D;
-    hipLaunchKernelGGL(k_head_wreduce, dim3((unsigned)((n + HWG - 1) / HWG)), dim3(HWG), 0, st, ws + P.dw_off,
-                       ws + P.db_off, P.splits, D, K, P.Kp, dW, dbias);
-    if (const int rc = bcnf_rt::launched()) return rc;
+    return launch<k_head_wreduce>(dim3((unsigned)((n + HWG - 1) / HWG)), dim3(HWG), 0, st, ws + P.dw_off, ws + P.db_off,
+                                  P.splits, D, K, P.Kp, dW, dbias);
   }
   return BCNF_OK;
 }
@@ -352,9 +346,8 @@ int bcnf_hybrid_finalize(float* loss_vals, const void* work, int64_t B, int32_t 
   HeadPlan P;
   if (!loss_vals || !work || !(weight >= 0.f) || !head_plan(B, 1, D, &P)) return BCNF_ERR_ARG;
   const float* ws = static_cast<const float*>(work);
-  hipLaunchKernelGGL(k_hybrid_finalize, dim3(1), dim3(HWG), 0, (hipStream_t)stream, loss_vals, ws + P.mse_off,
-                     P.n_mse, (long long)B, D, weight, guard);
-  return bcnf_rt::launched();
+  return launch<k_hybrid_finalize>(dim3(1), dim3(HWG), 0, (hipStream_t)stream, loss_vals, ws + P.mse_off, P.n_mse,
+                                   (long long)B, D, weight, guard);
 }
 
 }  // extern "C"

@@ -243,13 +243,10 @@ int bcnf_resimulate(const void* y_hat, int32_t y_hat_f64, int64_t n_draws, int64
   a.x = x;
   a.attempts = attempts;
   a.status = status;
-  if (y_hat_f64)
-    hipLaunchKernelGGL(k_resim<double>, dim3((unsigned)nwg), dim3(RWG), 0, (hipStream_t)stream, a,
-                       (const double*)y_hat);
-  else
-    hipLaunchKernelGGL(k_resim<float>, dim3((unsigned)nwg), dim3(RWG), 0, (hipStream_t)stream, a,
-                       (const float*)y_hat);
-  return bcnf_rt::launched();
+  return y_hat_f64 ? bcnf_rt::launch<k_resim<double>>(dim3((unsigned)nwg), dim3(RWG), 0, (hipStream_t)stream, a,
+                                                      (const double*)y_hat)
+                   : bcnf_rt::launch<k_resim<float>>(dim3((unsigned)nwg), dim3(RWG), 0, (hipStream_t)stream, a,
+                                                     (const float*)y_hat);
 }
 
 }  // extern "C"

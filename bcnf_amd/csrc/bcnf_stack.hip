@@ -19,7 +19,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <mutex>
 #include <utility>
 #include <vector>
 
@@ -35,7 +34,7 @@
 
 namespace {
 
-constexpr int NC16_MAX = 16;           // C <= 256: register-resident column tiles of k_hp / k_dh / k_dw1h            // tiles: D_1..D_NH, D_T, D_S, A_0..A_NH, PA, GA, PB, GB
+constexpr int NC16_MAX = 16;           // C <= 256: register-resident column tiles of k_hp / k_dh / dw1h_body         // tiles: D_1..D_NH, D_T, D_S, A_0..A_NH, PA, GA, PB, GB
 // Backward LDS tile of [16 samples s][16 columns r], unpadded: the four samples 4 t + q (t = 0..3) of column r sit in
 // the 16-B slot tile_slot(r, q) = 4 r + ((q + (r >> 1)) & 3), so the MFMA operand of lane (q, r) for the four K-steps t
 // is ONE 16-B read at 4 tile_slot(r, q), and each ds_read_b128 lane group covers all 16 slot banks (conflict-free). The
@@ -69,16 +68,8 @@ int round_rec(int n) {            // multiple of 4 floats with odd quotient (con
 
 // Broadcast-form sections (row_newbcast DPP, D_a = 10 / D_b = 9 stacks only): QBC_W1 Linear 1 (forward), QBC_MIX
 // the mix Q / Q^T (forward, inverse, backward), QBC_HEAD the T / S heads' transposes (backward).
-#ifndef BCNF_QBC_MASK
-#define BCNF_QBC_MASK 7
-#endif
 constexpr int QBC_W1 = 1, QBC_MIX = 2, QBC_HEAD = 4;
-// the kernels' test of a section's form (BCNF_QBC_CONST: a compile-time answer, for layout-specific A/B builds)
-#ifdef BCNF_QBC_CONST
-#define QBC_DEV(L, bit) (BCNF_QBC_CONST != 0)
-#else
-#define QBC_DEV(L, bit) (((L).qbc & (bit)) != 0)
-#endif
+#define QBC_DEV(L, bit) (((L).qbc & (bit)) != 0)   // the kernels' test of a section's form
 
 int make_layout(const BcnfStackDesc* d, BcnfLayout* L) {
   if (!d || !L) return BCNF_ERR_ARG;
@@ -116,7 +107,7 @@ int make_layout(const BcnfStackDesc* d, BcnfLayout* L) {
   L->cblk = L->blk_stride - L->H[1] * L->C;
   L->blk_pad = (L->cblk + 3) & ~3;
   L->sblk = slab_blk_floats(L->NH);
-  L->qbc = (L->Da == 10 && L->Db == 9) ? BCNF_QBC_MASK : 0;
+  L->qbc = (L->Da == 10 && L->Db == 9) ? (QBC_W1 | QBC_MIX | QBC_HEAD) : 0;
   L->p = d->dropout;
   L->keep_scale = (d->dropout > 0.f) ? (1.0f / (1.0f - d->dropout)) : 1.0f;
   const double t32 = std::min(4294967295.0, floor((double)d->dropout * 4294967296.0 + 0.5));   // dropout_bits
@@ -167,7 +158,8 @@ size_t fwd2_lds_bytes(const BcnfLayout& L, bool raw = false) {  // k_forward: re
 size_t bwd_lds_bytes(const BcnfLayout& L) {   // backward record ring, delta tiles (2), activation tiles (3), derivative slots (2)
   return sizeof(float) * (size_t)(2 * RING + 2 * (L.NH + 6) * TILE + 3 * (L.NH + 1) * TILE + 2 * 3 * 4 * 256);
 }
-constexpr size_t LDS_MAX = 160 * 1024;
+using bcnf_rt::launch;
+using bcnf_rt::LDS_MAX;
 
 bool layout_supported(const BcnfLayout& L, const BcnfStackDesc* d) {
   if (d->two_way) return false;
@@ -176,7 +168,7 @@ bool layout_supported(const BcnfLayout& L, const BcnfStackDesc* d) {
   for (int l = 1; l <= L.NH; ++l)
     if (L.H[l] > 16) return false;
   if (L.C < 1 || L.Cp > 16 * NC16_MAX) return false;
-  if (sizeof(float) * (size_t)(64 * 132 + 128 * (L.Cp + 32)) > LDS_MAX) return false;   // k_dw1h staging
+  if (sizeof(float) * (size_t)(64 * 132 + 128 * (L.Cp + 32)) > LDS_MAX) return false;   // dw1h_body staging
   if (16 * L.RF > 4 * 4 * BCNF_WG || 16 * L.RB > 4 * 4 * BCNF_WG) return false;
   if (fwd_lds_bytes(L) > LDS_MAX || bwd_lds_bytes(L) > LDS_MAX) return false;
   return true;
@@ -991,14 +983,6 @@ __device__ __forceinline__ void dw1h_body(const BcnfLayout& L, const float* __re
   }
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(BCNF_WG) void k_dw1h(BcnfLayout L, const float* __restrict__ d1,
-                                                  const float* __restrict__ h, long long B, int rows_per_split,
-                                                  float* __restrict__ work) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  dw1h_body<VEC>(L, d1, h, B, rows_per_split, work, blockIdx.x, blockIdx.y, smem);
-}
-
 size_t hp_lds_bytes() { return sizeof(float) * (size_t)(64 * KCP + KC * BNS); }
 size_t dh_lds_bytes() { return sizeof(float) * (size_t)(64 * KCP + KC * 16); }
 size_t dw1h_lds_bytes(const BcnfLayout& L) { return sizeof(float) * (size_t)(64 * KCP + KC * bstride16(L.Cp)); }
@@ -1446,33 +1430,9 @@ __device__ __forceinline__ void mlp_forward(const BcnfLayout& L, const float* __
   rot16x2(a, rr + F::T, T, a, rr + F::S, Sp);
 }
 
-// The same with the dropout multipliers as floats (msk[l - 1] = keep_scale or 0 for hidden layer l, drawn by
-// k_forward's helper waves): no bit extraction on the compute wave's chain.
-template <int NH, bool KEEP, bool DROP>
-__device__ __forceinline__ void mlp_forward_m(const float* __restrict__ rr, float x, float hp,
-                                              const float* __restrict__ msk, float& T, float& Sp, float* act, float* gd) {
-  using F = RecF<NH>;
-  float a = x;
-#pragma unroll
-  for (int l = 1; l <= NH; ++l) {
-    const float* w = (l == 1) ? rr + F::W1 : rr + F::HID + 17 * (l - 2);
-    const float pre = rot16(a, w, (l == 1) ? hp : w[16]);
-    if (KEEP) {
-      float g, dg;
-      gelu_fg(pre, g, dg);
-      a = DROP ? g * msk[l - 1] : g;
-      act[l - 1] = a;
-      gd[l - 1] = DROP ? dg * msk[l - 1] : dg;
-    } else {
-      a = DROP ? gelu_f(pre) * msk[l - 1] : gelu_f(pre);
-    }
-  }
-  T = rr[F::T + 16];
-  Sp = rr[F::S + 16];
-  rot16x2(a, rr + F::T, T, a, rr + F::S, Sp);
-}
-
-// Streamed form for k_forward's compute waves (r05). The record is read in consumption order: before stage l (hidden
+// Streamed form for k_forward's compute waves (r05), with the dropout multipliers as floats (msk[l - 1] = keep_scale
+// or 0 for hidden layer l, drawn by k_forward's helper waves: no bit extraction on the compute wave's chain).
+// The record is read in consumption order: before stage l (hidden
 // layer l = 1..NH, then NH + 1 = the T / S heads, NH + 2 = the mix) the wave issues the quads stage l + FWD_AHEAD
 // ends in, behind a scheduling barrier, so each lgkmcnt wait covers reads issued two layers earlier. (r04's
 // burst form ld_rec<FWD_HEAD, USED> let hipcc issue 17 reads after layer 1 and wait for all of them at once, then
@@ -2789,9 +2749,6 @@ __global__ __launch_bounds__(BWD_WG) void k_backward(BcnfLayout L, const float* 
     bwd_grad_jobs<NH>(dT, aT, slab, hw);                     // block 0 (tiles of the last interval)
   } else {
     const int tid = t8;
-#ifdef BCNF_BWD_PRIO
-    __builtin_amdgcn_s_setprio(BCNF_BWD_PRIO);
-#endif
     const long long b = (long long)blockIdx.x * 16 + s;
     const bool valid = b < B;
     const long long bc = valid ? b : B - 1;
@@ -3104,39 +3061,8 @@ __global__ __launch_bounds__(BCNF_WG) void k_fill_lds(float value) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Launch helpers
+// Launch helpers (every launch: bcnf_rt::launch, bcnf_device.h)
 // ------------------------------------------------------------------------------------------------
-int check_launch() { return bcnf_rt::launched(); }
-
-
-
-// Raise a kernel's dynamic-LDS limit once (cached per kernel; safe to call under stream capture
-// after the first eager call has set it).
-std::mutex g_attr_mu;
-const void* g_attr_fn[256];
-size_t g_attr_lds[256];
-int g_attr_n = 0;
-
-template <typename K>
-int launch_lds(K kernel, size_t& lds) {
-  if (lds > LDS_MAX) return BCNF_ERR_UNSUPPORTED;
-  const void* fn = reinterpret_cast<const void*>(kernel);
-  std::lock_guard<std::mutex> lk(g_attr_mu);
-  for (int i = 0; i < g_attr_n; ++i)
-    if (g_attr_fn[i] == fn && g_attr_lds[i] >= lds) return BCNF_OK;
-  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return bcnf_rt::hip_status(e);
-  int slot = -1;
-  for (int i = 0; i < g_attr_n; ++i)
-    if (g_attr_fn[i] == fn) slot = i;
-  if (slot < 0 && g_attr_n < 256) slot = g_attr_n++;
-  if (slot >= 0) {
-    g_attr_fn[slot] = fn;
-    g_attr_lds[slot] = lds;
-  }
-  return BCNF_OK;
-}
-
 template <int NH>
 bool layout_matches(const BcnfLayout& L) {
   return L.rf_b1 == RecF<NH>::B1 && L.rf_w1 == RecF<NH>::W1 && L.rf_hid == RecF<NH>::HID && L.rf_t == RecF<NH>::T &&
@@ -3145,85 +3071,52 @@ bool layout_matches(const BcnfLayout& L) {
          L.rb_an == RecB<NH>::AN && L.RB >= RecB<NH>::USED;
 }
 
-struct NllOut {
-  float* part = nullptr;
-};
-
 // float4 row loads: the row stride and the base are 16-byte aligned (columns >= C of a loaded float4 are
 // discarded by select, so a padded row's tail may hold anything).
 bool vec_rows(const BcnfLayout& L, const float* h) { return L.ldh % 4 == 0 && ((uintptr_t)h & 15) == 0; }
 
 int launch_hp(const BcnfLayout& L, const float* pk, const float* h, long long R, float* hp, hipStream_t st) {
-  size_t lds = hp_lds_bytes();
+  const size_t lds = hp_lds_bytes();
   const dim3 grid((unsigned)((R + 63) / 64), (unsigned)(L.NKp / 64));
-  int rc;
-  if (vec_rows(L, h)) {
-    if ((rc = launch_lds(k_hp<true>, lds))) return rc;
-    hipLaunchKernelGGL(k_hp<true>, grid, dim3(BCNF_WG), lds, st, L, pk, h, R, hp);
-  } else {
-    if ((rc = launch_lds(k_hp<false>, lds))) return rc;
-    hipLaunchKernelGGL(k_hp<false>, grid, dim3(BCNF_WG), lds, st, L, pk, h, R, hp);
-  }
-  return check_launch();
+  return vec_rows(L, h) ? launch<k_hp<true>>(grid, dim3(BCNF_WG), lds, st, L, pk, h, R, hp)
+                        : launch<k_hp<false>>(grid, dim3(BCNF_WG), lds, st, L, pk, h, R, hp);
 }
 
 template <int NH>
 int fwd_dispatch(const BcnfLayout& L, const float* pk, const float* y, const ProjArgs& P, long long B, float* z,
-                 float* ldj, float* logp, bool drop, const uint64_t* rng, float* arec, const NllOut& no,
-                 hipStream_t st, const RawArgs* raw = nullptr) {
+                 float* ldj, float* logp, bool drop, const uint64_t* rng, float* arec, float* part, hipStream_t st,
+                 const RawArgs* raw = nullptr) {
   if (!layout_matches<NH>(L)) return BCNF_ERR_ARG;
   if (P.Cp % 16 != 0 || P.Cp / 16 > HP_SMAX || P.C > P.Cp) return BCNF_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)((B + 15) / 16));
-  size_t lds = fwd2_lds_bytes(L, raw != nullptr);
+  const size_t lds = fwd2_lds_bytes(L, raw != nullptr);
   const bool save = arec != nullptr;
   const RawArgs R = raw ? *raw : RawArgs{};
-  int rc;
-#define BCNF_FWD(DR, SV, RW)                                                                                   \
-  rc = launch_lds(k_forward<NH, DR, SV, RW>, lds);                                                             \
-  if (rc) return rc;                                                                                           \
-  hipLaunchKernelGGL((k_forward<NH, DR, SV, RW>), grid, dim3(2 * BCNF_WG), lds, st, L, pk, y, P, B, z, ldj, logp, \
-                     rng, arec, no.part, R);
-  if (raw) {
-    if (!save) return BCNF_ERR_ARG;
-    if (drop) { BCNF_FWD(true, true, true) } else { BCNF_FWD(false, true, true) }
-  } else if (drop) {
-    if (save) { BCNF_FWD(true, true, false) } else { BCNF_FWD(true, false, false) }
-  } else {
-    if (save) { BCNF_FWD(false, true, false) } else { BCNF_FWD(false, false, false) }
-  }
-#undef BCNF_FWD
-  return check_launch();
+  // the six instantiations that exist: the pack-free forward always saves (k_forward<NH, *, false, true> is none)
+#define FWD(DR, SV, RW) \
+  launch<k_forward<NH, DR, SV, RW>>(grid, dim3(2 * BCNF_WG), lds, st, L, pk, y, P, B, z, ldj, logp, rng, arec, part, R)
+  if (raw) return !save ? BCNF_ERR_ARG : drop ? FWD(true, true, true) : FWD(false, true, true);
+  if (save) return drop ? FWD(true, true, false) : FWD(false, true, false);
+  return drop ? FWD(true, false, false) : FWD(false, false, false);
+#undef FWD
 }
 
 template <int NH>
 int inv_dispatch(const BcnfLayout& L, const float* pk, const float* zin, const float* hp, long long R,
                  const int64_t* ci, long long N, float* y, bool drop, const uint64_t* rng, hipStream_t st) {
   if (!layout_matches<NH>(L)) return BCNF_ERR_ARG;
-  int rc;
   if (!drop && L.RF == inv_m_rf<NH>() && L.PMB == (NH + 6) * 256 + (NH - 1) * 16 + 96) {   // eval: matrix cores
-    size_t lds_m = sizeof(float) * (size_t)(2 * RING);
+    const size_t lds_m = sizeof(float) * (size_t)(2 * RING);
     const dim3 grid_m((unsigned)((N + INV_M_SPB - 1) / INV_M_SPB));
-    if (L.Da <= 12 && L.Db <= 12) {
-      if ((rc = launch_lds(k_inverse_mfma<NH, true>, lds_m))) return rc;
-      hipLaunchKernelGGL((k_inverse_mfma<NH, true>), grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y);
-    } else {
-      if ((rc = launch_lds(k_inverse_mfma<NH, false>, lds_m))) return rc;
-      hipLaunchKernelGGL((k_inverse_mfma<NH, false>), grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y);
-    }
-    return check_launch();
+    float* const none = nullptr;   // no ldj / log_prob outputs
+    return L.Da <= 12 && L.Db <= 12
+               ? launch<k_inverse_mfma<NH, true>>(grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y, none, none)
+               : launch<k_inverse_mfma<NH, false>>(grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y, none, none);
   }
   const dim3 grid((unsigned)((N + 15) / 16));
-  size_t lds = fwd_lds_bytes(L);
-  if (drop) {
-    rc = launch_lds(k_inverse<NH, true>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_inverse<NH, true>), grid, dim3(BCNF_WG), lds, st, L, pk, zin, hp, R, ci, N, y, rng);
-  } else {
-    rc = launch_lds(k_inverse<NH, false>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_inverse<NH, false>), grid, dim3(BCNF_WG), lds, st, L, pk, zin, hp, R, ci, N, y, rng);
-  }
-  return check_launch();
+  const size_t lds = fwd_lds_bytes(L);
+  return drop ? launch<k_inverse<NH, true>>(grid, dim3(BCNF_WG), lds, st, L, pk, zin, hp, R, ci, N, y, rng)
+              : launch<k_inverse<NH, false>>(grid, dim3(BCNF_WG), lds, st, L, pk, zin, hp, R, ci, N, y, rng);
 }
 
 // The eval inverse that also returns the forward's log|det J| at y (and log_prob): matrix-core layouts only -- every
@@ -3234,19 +3127,11 @@ int inv_ldj_dispatch(const BcnfLayout& L, const float* pk, const float* zin, con
                      const int64_t* ci, long long N, float* y, float* ldj, float* logp, hipStream_t st) {
   if (!layout_matches<NH>(L)) return BCNF_ERR_ARG;
   if (L.RF != inv_m_rf<NH>() || L.PMB != (NH + 6) * 256 + (NH - 1) * 16 + 96) return BCNF_ERR_UNSUPPORTED;
-  int rc;
-  size_t lds_m = sizeof(float) * (size_t)(2 * RING);
+  const size_t lds_m = sizeof(float) * (size_t)(2 * RING);
   const dim3 grid_m((unsigned)((N + INV_M_SPB - 1) / INV_M_SPB));
-  if (L.Da <= 12 && L.Db <= 12) {
-    if ((rc = launch_lds(k_inverse_mfma<NH, true, true>, lds_m))) return rc;
-    hipLaunchKernelGGL((k_inverse_mfma<NH, true, true>), grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y,
-                       ldj, logp);
-  } else {
-    if ((rc = launch_lds(k_inverse_mfma<NH, false, true>, lds_m))) return rc;
-    hipLaunchKernelGGL((k_inverse_mfma<NH, false, true>), grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y,
-                       ldj, logp);
-  }
-  return check_launch();
+  return L.Da <= 12 && L.Db <= 12
+             ? launch<k_inverse_mfma<NH, true, true>>(grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y, ldj, logp)
+             : launch<k_inverse_mfma<NH, false, true>>(grid_m, dim3(INV_M_WG), lds_m, st, L, pk, zin, hp, R, ci, N, y, ldj, logp);
 }
 
 long long slab_stride_of(const BcnfLayout& L) { return (long long)L.nb * L.sblk; }
@@ -3257,30 +3142,31 @@ int bwd_dispatch(const BcnfLayout& L, const float* pk, const float* dz, const fl
                  const float* part, float* loss_out, uint64_t* rng_w, int32_t* guard, hipStream_t st) {
   if (!layout_matches<NH>(L)) return BCNF_ERR_ARG;
   const dim3 grid((unsigned)((B + 15) / 16));
-  size_t lds = bwd_lds_bytes(L);
-  const int rc = launch_lds(k_backward<NH>, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_backward<NH>), grid, dim3(BWD_WG), lds, st, L, pk, dz, dldj, dloss, nll, B, arec, dy,
-                     d1, slab, stride, part, loss_out, rng_w, guard);
-  return check_launch();
+  return launch<k_backward<NH>>(grid, dim3(BWD_WG), bwd_lds_bytes(L), st, L, pk, dz, dldj, dloss, nll, B, arec, dy, d1,
+                                slab, stride, part, loss_out, rng_w, guard);
 }
 
 // split-K geometry of the W1 condition-part gradient
-int w1h_rows_per_split(long long) { return KC; }   // one LDS chunk of rows per split
-long long w1h_splits(long long B) { return (B + w1h_rows_per_split(B) - 1) / w1h_rows_per_split(B); }
+constexpr int W1H_ROWS_PER_SPLIT = KC;   // one LDS chunk of rows per split
+long long w1h_splits(long long B) { return (B + W1H_ROWS_PER_SPLIT - 1) / W1H_ROWS_PER_SPLIT; }
 long long w1h_work_floats(const BcnfLayout& L, long long B) { return w1h_splits(B) * L.nb * 16LL * L.Cp; }
 
 // Workspace (floats): [activation records nb*B*16*AR][loss partials][HP nb*B*16][D1 nb*B*16]
-// (`drop` no longer changes the layout: the records hold the masked activations)
-long long ws_part_off(const BcnfLayout& L, long long B, bool) {
+// (the same with and without dropout: the records hold the masked activations)
+long long ws_part_off(const BcnfLayout& L, long long B) {
   return (long long)L.nb * ((B + 15) / 16) * BCNF_WG * act_rec_floats(L.NH);   // padded rows own slots
 }
-long long ws_hp_off(const BcnfLayout& L, long long B, bool drop) {
-  return ws_part_off(L, B, drop) + (((B + 15) / 16 + 3) & ~3LL);
+long long ws_hp_off(const BcnfLayout& L, long long B) { return ws_part_off(L, B) + (((B + 15) / 16 + 3) & ~3LL); }
+long long ws_d1_off(const BcnfLayout& L, long long B) { return ws_hp_off(L, B) + (long long)L.nb * B * 16; }
+long long ws_floats(const BcnfLayout& L, long long B) {
+  return ws_d1_off(L, B) + (long long)L.nb * B * 16 + 16;   // + D1 dummy row
 }
-long long ws_d1_off(const BcnfLayout& L, long long B, bool drop) { return ws_hp_off(L, B, drop) + (long long)L.nb * B * 16; }
-long long ws_floats(const BcnfLayout& L, long long B, bool drop) {
-  return ws_d1_off(L, B, drop) + (long long)L.nb * B * 16 + 16;   // + D1 dummy row
+
+// The prologue of an entry that runs a stack: its layout, or the status of a malformed / unsupported description.
+int stack_setup(const BcnfStackDesc* desc, BcnfLayout* L) {
+  const int rc = make_layout(desc, L);
+  if (rc) return rc;
+  return layout_supported(*L, desc) ? BCNF_OK : BCNF_ERR_UNSUPPORTED;
 }
 
 int forward_impl(const BcnfStackDesc* desc, const void* packed, const float* y, const float* h, int64_t batch,
@@ -3288,9 +3174,8 @@ int forward_impl(const BcnfStackDesc* desc, const void* packed, const float* y, 
                  bool save, bool nll, bool finalize, float* loss_out, int32_t* guard, void* stream,
                  const float* fold = nullptr, int X = 0, int ldx = 0, const RawArgs* raw = nullptr) {
   BcnfLayout L;
-  int rc = make_layout(desc, &L);
+  int rc = stack_setup(desc, &L);
   if (rc) return rc;
-  if (!layout_supported(L, desc)) return BCNF_ERR_UNSUPPORTED;
   if (batch < 0) return BCNF_ERR_ARG;
   if (batch == 0) return nll ? BCNF_ERR_ARG : BCNF_OK;      // the mean over an empty batch is undefined
   if (!packed || !y || !h || !z || !workspace) return BCNF_ERR_ARG;
@@ -3299,8 +3184,7 @@ int forward_impl(const BcnfStackDesc* desc, const void* packed, const float* y, 
   if (drop && !rng_state) return BCNF_ERR_ARG;
   float* ws = (float*)workspace;
   float* arec = (save || nll) ? ws : nullptr;
-  NllOut no;
-  if (nll) no.part = ws + ws_part_off(L, batch, drop);
+  float* part = nll ? ws + ws_part_off(L, batch) : nullptr;
   const float* pk = (const float*)packed;
   hipStream_t st = (hipStream_t)stream;
   // the condition projection runs inside k_forward: h, or x with the folded feature Linear (fold_layout: Wc / bc
@@ -3309,15 +3193,14 @@ int forward_impl(const BcnfStackDesc* desc, const void* packed, const float* y, 
   const float* pbase = fold ? fold : pk;
   const ProjArgs P{h, pbase + Lp.w1c_off, pbase + Lp.b1c_off, (long long)Lp.ldh, Lp.C, Lp.Cp, Lp.NKp};
   switch (L.NH) {
-#define BCNF_CASE(N) case N: rc = fwd_dispatch<N>(L, pk, y, P, batch, z, ldj, log_prob, drop, rng_state, arec, no, st, raw); break;
+#define BCNF_CASE(N) case N: rc = fwd_dispatch<N>(L, pk, y, P, batch, z, ldj, log_prob, drop, rng_state, arec, part, st, raw); break;
     BCNF_CASE(1) BCNF_CASE(2) BCNF_CASE(3) BCNF_CASE(4) BCNF_CASE(5) BCNF_CASE(6) BCNF_CASE(7) BCNF_CASE(8)
 #undef BCNF_CASE
     default: return BCNF_ERR_UNSUPPORTED;
   }
   if (rc || !nll || !finalize) return rc;
-  hipLaunchKernelGGL(k_nll_finalize, dim3(1), dim3(BCNF_WG), 0, st, (const float*)no.part, (int)((batch + 15) / 16),
-                     (long long)batch, loss_out, drop ? const_cast<uint64_t*>(rng_state) : nullptr, guard);
-  return check_launch();
+  return launch<k_nll_finalize>(dim3(1), dim3(BCNF_WG), 0, st, (const float*)part, (int)((batch + 15) / 16),
+                                (long long)batch, loss_out, drop ? const_cast<uint64_t*>(rng_state) : nullptr, guard);
 }
 
 int backward_impl(const BcnfStackDesc* desc, const void* packed, const float* h, const float* dz, const float* dldj,
@@ -3334,8 +3217,7 @@ extern "C" {
 
 int bcnf_stack_supported(const BcnfStackDesc* desc) {
   BcnfLayout L;
-  if (make_layout(desc, &L) != BCNF_OK) return 0;
-  return layout_supported(L, desc) ? 1 : 0;
+  return stack_setup(desc, &L) == BCNF_OK ? 1 : 0;
 }
 
 int bcnf_param_count(const BcnfStackDesc* desc, int64_t* n_trainable, int64_t* n_frozen) {
@@ -3361,7 +3243,7 @@ int bcnf_workspace_bytes(const BcnfStackDesc* desc, int64_t batch, int32_t train
   const int rc = make_layout(desc, &L);
   if (rc) return rc;
   if (!bytes || batch < 0) return BCNF_ERR_ARG;
-  *bytes = ws_floats(L, batch, training && L.p > 0.f) * 4;
+  *bytes = ws_floats(L, batch) * 4;
   return BCNF_OK;
 }
 
@@ -3385,14 +3267,11 @@ int bcnf_inverse_scratch_bytes(const BcnfStackDesc* desc, int64_t h_rows, int64_
 
 int bcnf_pack_params(const BcnfStackDesc* desc, const float* params, const float* qmats, void* packed, void* stream) {
   BcnfLayout L;
-  int rc = make_layout(desc, &L);
+  const int rc = stack_setup(desc, &L);
   if (rc) return rc;
-  if (!layout_supported(L, desc)) return BCNF_ERR_UNSUPPORTED;
   if (!params || !packed || (L.nb > 1 && !qmats)) return BCNF_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
   const int npw = pack_wgs(L);
-  hipLaunchKernelGGL(k_pack, dim3(npw + 1), dim3(BCNF_WG), 0, st, L, params, qmats, (float*)packed, npw);
-  return check_launch();
+  return launch<k_pack>(dim3(npw + 1), dim3(BCNF_WG), 0, (hipStream_t)stream, L, params, qmats, (float*)packed, npw);
 }
 
 int bcnf_stack_forward(const BcnfStackDesc* desc, const void* packed, const float* y, const float* h, int64_t batch,
@@ -3429,17 +3308,15 @@ int bcnf_backward_tail(const BcnfStackDesc* desc, const void* packed, const void
                        const void* workspace, int64_t batch, int32_t training, float* dh, float* dparams,
                        void* stream) {
   BcnfLayout L;
-  int rc = make_layout(desc, &L);
+  int rc = stack_setup(desc, &L);
   if (rc) return rc;
-  if (!layout_supported(L, desc)) return BCNF_ERR_UNSUPPORTED;
   if (!packed || !slab || !h || !workspace || !dparams || batch < 1) return BCNF_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const long long S = slab_stride_of(L);
   const int nwg = (int)((batch + 15) / 16);
-  const bool drop = training && L.p > 0.f;
-  const float* d1 = (const float*)workspace + ws_d1_off(L, batch, drop);
+  const float* d1 = (const float*)workspace + ws_d1_off(L, batch);
   float* work = (float*)slab + (long long)nwg * S;
-  const int rps = w1h_rows_per_split(batch);
+  const int rps = W1H_ROWS_PER_SPLIT;
   const long long splits = w1h_splits(batch);
   TailGrid G;
   G.gx_dh = (int)((batch + 63) / 64);
@@ -3450,28 +3327,21 @@ int bcnf_backward_tail(const BcnfStackDesc* desc, const void* packed, const void
   size_t lds = dw1h_lds_bytes(L);
   if (dh_lds_bytes() > lds) lds = dh_lds_bytes();
   const dim3 grid((unsigned)(G.n_dh + G.n_red + n_dw));
-  if (vec_rows(L, h)) {
-    if ((rc = launch_lds(k_bwd_tail<true>, lds))) return rc;
-    hipLaunchKernelGGL(k_bwd_tail<true>, grid, dim3(BCNF_WG), lds, st, L, G, (const float*)packed, d1, h,
-                       (long long)batch, dh, (const float*)slab, S, nwg, dparams, rps, work);
-  } else {
-    if ((rc = launch_lds(k_bwd_tail<false>, lds))) return rc;
-    hipLaunchKernelGGL(k_bwd_tail<false>, grid, dim3(BCNF_WG), lds, st, L, G, (const float*)packed, d1, h,
-                       (long long)batch, dh, (const float*)slab, S, nwg, dparams, rps, work);
-  }
-  if ((rc = check_launch())) return rc;
+  rc = vec_rows(L, h) ? launch<k_bwd_tail<true>>(grid, dim3(BCNF_WG), lds, st, L, G, (const float*)packed, d1, h,
+                                                 (long long)batch, dh, (const float*)slab, S, nwg, dparams, rps, work)
+                      : launch<k_bwd_tail<false>>(grid, dim3(BCNF_WG), lds, st, L, G, (const float*)packed, d1, h,
+                                                  (long long)batch, dh, (const float*)slab, S, nwg, dparams, rps, work);
+  if (rc) return rc;
   const long long outs = (long long)L.nb * 16 * L.Cp;
-  hipLaunchKernelGGL(k_dw1h_reduce, dim3((unsigned)((outs + BCNF_WG - 1) / BCNF_WG)), dim3(BCNF_WG), 0, st, L,
-                     (const float*)work, (int)splits, dparams);
-  return check_launch();
+  return launch<k_dw1h_reduce>(dim3((unsigned)((outs + BCNF_WG - 1) / BCNF_WG)), dim3(BCNF_WG), 0, st, L,
+                               (const float*)work, (int)splits, dparams);
 }
 
 // ---- folded linear feature network (see fold_body) ----
 namespace {
 int fold_setup(const BcnfStackDesc* desc, int32_t X, BcnfLayout* L) {
-  int rc = make_layout(desc, L);
+  const int rc = stack_setup(desc, L);
   if (rc) return rc;
-  if (!layout_supported(*L, desc)) return BCNF_ERR_UNSUPPORTED;
   if (X < 1 || fold_xp(X) > 16 * NC16_MAX) return BCNF_ERR_UNSUPPORTED;
   if (dw1h_lds_bytes(fold_layout(*L, X, X)) > LDS_MAX) return BCNF_ERR_UNSUPPORTED;
   return BCNF_OK;
@@ -3523,9 +3393,8 @@ int bcnf_pack_params_fold(const BcnfStackDesc* desc, const float* params, const 
   }
   const int npw = pack_wgs(L, true);
   const unsigned grid = (unsigned)(L.NKp / 16 * FOLD_SPLIT + ga.nwg + npw + 1);
-  hipLaunchKernelGGL(k_pack_fold, dim3(grid), dim3(BCNF_WG), 0, (hipStream_t)stream, L, params, qmats, (float*)packed,
-                     feat_weight, feat_bias, (int)in_features, fold, ga, npw);
-  return check_launch();
+  return launch<k_pack_fold>(dim3(grid), dim3(BCNF_WG), 0, (hipStream_t)stream, L, params, qmats, (float*)packed,
+                             feat_weight, feat_bias, (int)in_features, fold, ga, npw);
 }
 
 int bcnf_fold_nll_forward(const BcnfStackDesc* desc, const void* packed, const float* fold, int32_t in_features,
@@ -3541,11 +3410,7 @@ int bcnf_fold_nll_forward(const BcnfStackDesc* desc, const void* packed, const f
 }
 
 int bcnf_lds_fill(float value, void* stream) {
-  size_t lds = LDS_MAX;
-  const int rc = launch_lds(k_fill_lds, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_fill_lds, dim3(4 * 256), dim3(BCNF_WG), LDS_MAX, (hipStream_t)stream, value);
-  return check_launch();
+  return launch<k_fill_lds>(dim3(4 * 256), dim3(BCNF_WG), LDS_MAX, (hipStream_t)stream, value);
 }
 
 int bcnf_fold_raw_table_bytes(const BcnfStackDesc* desc, int32_t in_features, int64_t* bytes) {
@@ -3649,12 +3514,11 @@ int bcnf_fold_backward_tail(const BcnfStackDesc* desc, const void* packed, const
   hipStream_t st = (hipStream_t)stream;
   const long long S = slab_stride_of(L);
   const int nwg = (int)((batch + 15) / 16);
-  const bool drop = training && L.p > 0.f;
-  const float* d1 = (const float*)workspace + ws_d1_off(L, batch, drop);
+  const float* d1 = (const float*)workspace + ws_d1_off(L, batch);
   float* work = (float*)slab + (long long)nwg * S;
   float* gx = work + w1h_work_floats(F, batch);
   A.asc = gx + (long long)L.nb * 16 * F.Cp;
-  const int rps = w1h_rows_per_split(batch);
+  const int rps = W1H_ROWS_PER_SPLIT;
   const long long splits = w1h_splits(batch);
   float* wf1 = A.asc + 4;                              // [Wf | bf] as k_fold_finish's role a reads them
   const float* bf1 = feat_bias ? wf1 + (long long)L.C * in_features : nullptr;
@@ -3666,29 +3530,20 @@ int bcnf_fold_backward_tail(const BcnfStackDesc* desc, const void* packed, const
   if (lds < sizeof(float) * RED_SMEM) lds = sizeof(float) * RED_SMEM;
   const bool vec = vec_rows(F, x);
   const bool nt3 = (F.Cp >> 4) <= 6;                   // column tiles per wave: 3 (Xp <= 96: FC_small) or 8
-#define BCNF_FOLD_TAIL(V, NT)                                                                                      \
-  do {                                                                                                             \
-    if ((rc = launch_lds(k_fold_tail<V, NT>, lds))) return rc;                                                     \
-    hipLaunchKernelGGL((k_fold_tail<V, NT>), grid, dim3(BCNF_WG), lds, st, L, F, d1, x, (long long)batch, rps, work, \
-                       gx_dw, (int)n_sk, (int)in_features, (const float*)slab, S, nwg, dparams, feat_weight,       \
-                       feat_bias, wf1, A);                                                                         \
-  } while (0)
-  if (vec && nt3) BCNF_FOLD_TAIL(true, 3);
-  else if (vec) BCNF_FOLD_TAIL(true, 8);
-  else if (nt3) BCNF_FOLD_TAIL(false, 3);
-  else BCNF_FOLD_TAIL(false, 8);
-#undef BCNF_FOLD_TAIL
-  if ((rc = check_launch())) return rc;
+#define FOLD_TAIL(V, NT)                                                                                          \
+  launch<k_fold_tail<V, NT>>(grid, dim3(BCNF_WG), lds, st, L, F, d1, x, (long long)batch, rps, work, gx_dw, (int)n_sk, \
+                             (int)in_features, (const float*)slab, S, nwg, dparams, feat_weight, feat_bias, wf1, A)
+  rc = vec ? (nt3 ? FOLD_TAIL(true, 3) : FOLD_TAIL(true, 8)) : (nt3 ? FOLD_TAIL(false, 3) : FOLD_TAIL(false, 8));
+#undef FOLD_TAIL
+  if (rc) return rc;
   const long long total = (long long)L.nb * 16 * F.Cp;
-  hipLaunchKernelGGL(k_fold_gx, dim3((unsigned)((total + BCNF_WG - 1) / BCNF_WG)), dim3(BCNF_WG), 0, st, total,
-                     (const float*)work, (int)splits, gx);
-  if ((rc = check_launch())) return rc;
+  rc = launch<k_fold_gx>(dim3((unsigned)((total + BCNF_WG - 1) / BCNF_WG)), dim3(BCNF_WG), 0, st, total,
+                         (const float*)work, (int)splits, gx);
+  if (rc) return rc;
   const int n_fin = (L.nb + (F.Cp >> 4)) * (L.Cp >> 4);
-  size_t fin_lds = sizeof(float) * FIN_SMEM;
-  if ((rc = launch_lds(k_fold_finish, fin_lds))) return rc;
-  hipLaunchKernelGGL(k_fold_finish, dim3((unsigned)n_fin), dim3(BCNF_WG), fin_lds, st, L, (const float*)packed,
-                     (const float*)gx, (const float*)wf1, bf1, (int)in_features, dparams, dfeat_weight, dfeat_bias, A);
-  return check_launch();
+  return launch<k_fold_finish>(dim3((unsigned)n_fin), dim3(BCNF_WG), sizeof(float) * FIN_SMEM, st, L,
+                               (const float*)packed, (const float*)gx, (const float*)wf1, bf1, (int)in_features,
+                               dparams, dfeat_weight, dfeat_bias, A);
 }
 
 int bcnf_grad_reduce(const BcnfStackDesc* desc, const void* slab, const float* h, const void* workspace,
@@ -3700,26 +3555,21 @@ int bcnf_grad_reduce(const BcnfStackDesc* desc, const void* slab, const float* h
 int bcnf_stack_dh(const BcnfStackDesc* desc, const void* packed, const void* workspace, int64_t batch, int32_t training,
                   float* dh, void* stream) {
   BcnfLayout L;
-  int rc = make_layout(desc, &L);
+  const int rc = stack_setup(desc, &L);
   if (rc) return rc;
-  if (!layout_supported(L, desc)) return BCNF_ERR_UNSUPPORTED;
   if (batch < 0 || !packed || !workspace || !dh) return BCNF_ERR_ARG;
   if (batch == 0) return BCNF_OK;
-  const float* d1 = (const float*)workspace + ws_d1_off(L, batch, training && L.p > 0.f);
-  size_t lds = dh_lds_bytes();
-  if ((rc = launch_lds(k_dh, lds))) return rc;
-  hipLaunchKernelGGL(k_dh, dim3((unsigned)((batch + 63) / 64), (unsigned)(L.Cp >> 4)), dim3(BCNF_WG), lds,
-                     (hipStream_t)stream, L, (const float*)packed, d1, (long long)batch, dh);
-  return check_launch();
+  const float* d1 = (const float*)workspace + ws_d1_off(L, batch);
+  return launch<k_dh>(dim3((unsigned)((batch + 63) / 64), (unsigned)(L.Cp >> 4)), dim3(BCNF_WG), dh_lds_bytes(),
+                      (hipStream_t)stream, L, (const float*)packed, d1, (long long)batch, dh);
 }
 
 int bcnf_stack_inverse(const BcnfStackDesc* desc, const void* packed, const float* z, const float* h, int64_t h_rows,
                        const int64_t* cond_index, int64_t n_rows, float* y, int32_t training,
                        const uint64_t* rng_state, void* scratch, void* stream) {
   BcnfLayout L;
-  int rc = make_layout(desc, &L);
+  int rc = stack_setup(desc, &L);
   if (rc) return rc;
-  if (!layout_supported(L, desc)) return BCNF_ERR_UNSUPPORTED;
   if (n_rows == 0) return BCNF_OK;
   if (n_rows < 0 || h_rows < 1 || !packed || !z || !h || !y || !scratch) return BCNF_ERR_ARG;
   if (!cond_index && h_rows != n_rows) return BCNF_ERR_ARG;
@@ -3744,9 +3594,8 @@ int bcnf_stack_inverse_logdet(const BcnfStackDesc* desc, const void* packed, con
   if (desc->two_way) return BCNF_ERR_UNSUPPORTED;   // the reference's two_way inverse is not its forward's inverse
   if (!y || !ldj) return BCNF_ERR_ARG;
   BcnfLayout L;
-  int rc = make_layout(desc, &L);
+  int rc = stack_setup(desc, &L);
   if (rc) return rc;
-  if (!layout_supported(L, desc)) return BCNF_ERR_UNSUPPORTED;
   if (n_rows == 0) return BCNF_OK;
   if (n_rows < 0 || h_rows < 1 || !packed || !z || !h || !scratch) return BCNF_ERR_ARG;
   if (!cond_index && h_rows != n_rows) return BCNF_ERR_ARG;
@@ -3788,9 +3637,8 @@ int backward_impl(const BcnfStackDesc* desc, const void* packed, const float* h,
                   float* dh, float* dparams, void* slab, float* loss_out, uint64_t* rng_state, int32_t* guard,
                   void* stream) {
   BcnfLayout L;
-  int rc = make_layout(desc, &L);
+  int rc = stack_setup(desc, &L);
   if (rc) return rc;
-  if (!layout_supported(L, desc)) return BCNF_ERR_UNSUPPORTED;
   if (batch < 0 || !packed || !h || !workspace || !slab) return BCNF_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (batch == 0) {
@@ -3802,10 +3650,10 @@ int backward_impl(const BcnfStackDesc* desc, const void* packed, const float* h,
   const bool drop = training && L.p > 0.f;
   float* ws = (float*)workspace;
   const float* arec = ws;
-  float* d1 = ws + ws_d1_off(L, batch, drop);
+  float* d1 = ws + ws_d1_off(L, batch);
   const float* pk = (const float*)packed;
   const long long stride = slab_stride_of(L);
-  const float* part = ws + ws_part_off(L, batch, drop);
+  const float* part = ws + ws_part_off(L, batch);
   uint64_t* rng_w = (loss_out && drop) ? rng_state : nullptr;
   switch (L.NH) {
 #define BCNF_CASE(N) case N: rc = bwd_dispatch<N>(L, pk, dz, dldj, dloss, nll, batch, arec, dy, d1, (float*)slab, stride, part, loss_out, rng_w, guard, st); break;

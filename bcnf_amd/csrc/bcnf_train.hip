@@ -17,6 +17,8 @@
 
 namespace {
 
+using bcnf_rt::launch;
+
 constexpr int EPT = 4;                          // elements per thread in the elementwise kernels
 constexpr int CHUNK = BCNF_WG * EPT;            // elements per workgroup
 
@@ -476,25 +478,15 @@ __global__ __launch_bounds__(BCNF_WG) void k_lin(const float* __restrict__ A, in
 template <bool TB, bool SA, bool ACT>
 int launch_lin(const float* A, int lda, const float* Bm, int ldb, const float* bias, float* C, int ldc, long long M,
                int Nc, int R, const float* sa, const ActArgs& act, hipStream_t st) {
-  if (R <= LN_RMAX) {
+  if (R <= LN_RMAX) {   // the limit asked for is LN_RMAX's: the first (eager) call, before any capture, asks once
     constexpr size_t kmax = sizeof(float) * LN_RMAX * (LN_NT * 16 + 1);
-    static bool attr = false;                            // first (eager) call, before any capture
-    if (!attr) {
-      if (const int rc = bcnf_rt::hip_status(hipFuncSetAttribute((const void*)k_lin<TB, SA, ACT>,
-                                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kmax)))
-        return rc;
-      attr = true;
-    }
     const size_t lds = sizeof(float) * (size_t)R * (LN_NT * 16 + 1);
     const dim3 grid((unsigned)((M + 63) / 64), (unsigned)((Nc + LN_NT * 16 - 1) / (LN_NT * 16)));
-    hipLaunchKernelGGL((k_lin<TB, SA, ACT>), grid, dim3(BCNF_WG), lds, st, A, lda, Bm, ldb, bias, C, ldc, M, Nc, R, sa,
-                       act);
-  } else {
-    const dim3 grid((unsigned)((M + 63) / 64), (unsigned)((Nc + 15) / 16));
-    hipLaunchKernelGGL((k_gemm<TB, SA, ACT>), grid, dim3(BCNF_WG), 0, st, A, lda, Bm, ldb, bias, C, ldc, M, Nc, R, sa,
-                       act);
+    return launch<k_lin<TB, SA, ACT>>(grid, dim3(BCNF_WG), {lds, kmax}, st, A, lda, Bm, ldb, bias, C, ldc, M, Nc, R, sa,
+                                      act);
   }
-  return bcnf_rt::launched();
+  const dim3 grid((unsigned)((M + 63) / 64), (unsigned)((Nc + 15) / 16));
+  return launch<k_gemm<TB, SA, ACT>>(grid, dim3(BCNF_WG), 0, st, A, lda, Bm, ldb, bias, C, ldc, M, Nc, R, sa, act);
 }
 
 // Split-K weight gradient: work[s][n][k] = sum_{m in split s} dY[m][n] X[m][k],
@@ -591,8 +583,6 @@ __global__ __launch_bounds__(BCNF_WG) void k_wt_reduce(const float* __restrict__
   for (; s < splits; ++s) acc += src[(long long)s * stride];
   *dst = acc;
 }
-
-using bcnf_rt::launched;
 
 __global__ __launch_bounds__(BCNF_WG) void k_gather2(const int64_t* __restrict__ idx, int n, int rpw,
                                                      const float* __restrict__ s0, int c0, float* __restrict__ d0,
@@ -692,15 +682,13 @@ int bcnf_adam_step(int32_t n_tensors, float* const* params, float* const* grads,
     if (!T.p[i] || !T.m[i] || !T.v[i]) return BCNF_ERR_ARG;
   const long long total = T.start[T.n];
   const unsigned nwg = (unsigned)n_partials(total);
-  if (adam_groups(total) == BIG_G)
-    hipLaunchKernelGGL(k_adam<BIG_G>, dim3(nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, T, step, lr, beta1, beta2, eps,
-                       weight_decay, grad_partials, guard, AdamBook{});
-  else
-    hipLaunchKernelGGL(k_adam<1>, dim3(nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, T, step, lr, beta1, beta2, eps,
-                       weight_decay, grad_partials, guard, AdamBook{});
-  if ((rc = launched()) || !advance_step) return rc;
-  hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, (hipStream_t)stream, step, (long long*)nullptr, 0LL, guard);
-  return launched();
+  hipStream_t st = (hipStream_t)stream;
+  rc = adam_groups(total) == BIG_G ? launch<k_adam<BIG_G>>(dim3(nwg), dim3(BCNF_WG), 0, st, T, step, lr, beta1, beta2, eps,
+                                                           weight_decay, grad_partials, guard, AdamBook{})
+                                   : launch<k_adam<1>>(dim3(nwg), dim3(BCNF_WG), 0, st, T, step, lr, beta1, beta2, eps,
+                                                       weight_decay, grad_partials, guard, AdamBook{});
+  if (rc || !advance_step) return rc;
+  return launch<k_advance>(dim3(1), dim3(64), 0, st, step, (long long*)nullptr, 0LL, guard);
 }
 
 int bcnf_adam_step_bookkeep(int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
@@ -719,13 +707,11 @@ int bcnf_adam_step_bookkeep(int32_t n_tensors, float* const* params, float* cons
   const unsigned nwg = (unsigned)n_partials(total);
   const AdamBook bk{step, (long long*)advance_cursor, (long long)cursor_modulo, log_values, log_history,
                     (int*)done_counter};
-  if (adam_groups(total) == BIG_G)
-    hipLaunchKernelGGL(k_adam<BIG_G>, dim3(nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, T, step, lr, beta1, beta2, eps,
-                       weight_decay, (float*)nullptr, guard, bk);
-  else
-    hipLaunchKernelGGL(k_adam<1>, dim3(nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, T, step, lr, beta1, beta2, eps,
-                       weight_decay, (float*)nullptr, guard, bk);
-  return launched();
+  hipStream_t st = (hipStream_t)stream;
+  return adam_groups(total) == BIG_G ? launch<k_adam<BIG_G>>(dim3(nwg), dim3(BCNF_WG), 0, st, T, step, lr, beta1, beta2,
+                                                             eps, weight_decay, (float*)nullptr, guard, bk)
+                                     : launch<k_adam<1>>(dim3(nwg), dim3(BCNF_WG), 0, st, T, step, lr, beta1, beta2, eps,
+                                                         weight_decay, (float*)nullptr, guard, bk);
 }
 
 int bcnf_grad_sumsq(int32_t n_tensors, float* const* grads, const int64_t* numel, float* grad_partials, void* stream) {
@@ -734,11 +720,9 @@ int bcnf_grad_sumsq(int32_t n_tensors, float* const* grads, const int64_t* numel
   if (rc) return rc;
   if (!grad_partials) return BCNF_ERR_ARG;
   const unsigned nwg = (unsigned)n_partials(T.start[T.n]);
-  if (adam_groups(T.start[T.n]) == BIG_G)
-    hipLaunchKernelGGL(k_sumsq<BIG_G>, dim3(nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, T, grad_partials);
-  else
-    hipLaunchKernelGGL(k_sumsq<1>, dim3(nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, T, grad_partials);
-  return launched();
+  return adam_groups(T.start[T.n]) == BIG_G
+             ? launch<k_sumsq<BIG_G>>(dim3(nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, T, grad_partials)
+             : launch<k_sumsq<1>>(dim3(nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, T, grad_partials);
 }
 
 int bcnf_clip_grad_norm(int32_t n_tensors, float* const* grads, const int64_t* numel, const float* grad_partials,
@@ -753,21 +737,21 @@ int bcnf_clip_grad_norm(int32_t n_tensors, float* const* grads, const int64_t* n
   if (advance_cursor && cursor_modulo < 1) return BCNF_ERR_ARG;
   const float* part = grad_partials;
   int nread = (int)np;
+  hipStream_t st = (hipStream_t)stream;
   if (np > CLIP_DIRECT_PARTIALS) {      // pre-reduce into the extra slot
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(SP_WG), 0, (hipStream_t)stream, grad_partials, (int)np,
-                       const_cast<float*>(grad_partials) + np, guard);
+    rc = launch<k_sum_partials>(dim3(1), dim3(SP_WG), 0, st, grad_partials, (int)np,
+                                const_cast<float*>(grad_partials) + np, guard);
+    if (rc) return rc;
     part = grad_partials + np;
     nread = 1;
   }
-  if (adam_groups(T.start[T.n]) == BIG_G)
-    hipLaunchKernelGGL(k_clip<BIG_G>, dim3((unsigned)np), dim3(BCNF_WG), 0, (hipStream_t)stream, T, part, nread,
-                       max_norm, total_norm, advance_step, (long long*)advance_cursor, (long long)cursor_modulo,
-                       log_values, log_history, guard);
-  else
-    hipLaunchKernelGGL(k_clip<1>, dim3((unsigned)np), dim3(BCNF_WG), 0, (hipStream_t)stream, T, part, nread,
-                       max_norm, total_norm, advance_step, (long long*)advance_cursor, (long long)cursor_modulo,
-                       log_values, log_history, guard);
-  return launched();
+  return adam_groups(T.start[T.n]) == BIG_G
+             ? launch<k_clip<BIG_G>>(dim3((unsigned)np), dim3(BCNF_WG), 0, st, T, part, nread, max_norm, total_norm,
+                                     advance_step, (long long*)advance_cursor, (long long)cursor_modulo, log_values,
+                                     log_history, guard)
+             : launch<k_clip<1>>(dim3((unsigned)np), dim3(BCNF_WG), 0, st, T, part, nread, max_norm, total_norm,
+                                 advance_step, (long long*)advance_cursor, (long long)cursor_modulo, log_values,
+                                 log_history, guard);
 }
 
 namespace {
@@ -776,9 +760,8 @@ int gather_launch(const int64_t* idx, int64_t n, const float* src0, int32_t cols
   if (n * (int64_t)(cols0 + cols1) >= (1LL << 31)) return BCNF_ERR_UNSUPPORTED;
   int rpw, nwg;
   gather2_plan(n, &rpw, &nwg);
-  hipLaunchKernelGGL(k_gather2, dim3((unsigned)nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, idx,
-                     (int)n, rpw, src0, cols0, dst0, src1, cols1, dst1, (const long long*)cursor);
-  return launched();
+  return launch<k_gather2>(dim3((unsigned)nwg), dim3(BCNF_WG), 0, (hipStream_t)stream, idx, (int)n, rpw, src0, cols0,
+                           dst0, src1, cols1, dst1, (const long long*)cursor);
 }
 }  // namespace
 
@@ -799,9 +782,8 @@ int bcnf_gather_batch(const int64_t* order, const int64_t* cursor, int64_t batch
 
 int bcnf_advance_counters(float* step, int64_t* cursor, int64_t n_batches, void* stream) {
   if (cursor && n_batches < 1) return BCNF_ERR_ARG;
-  hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, (hipStream_t)stream, step, (long long*)cursor,
-                     (long long)n_batches, (const int32_t*)nullptr);
-  return launched();
+  return launch<k_advance>(dim3(1), dim3(64), 0, (hipStream_t)stream, step, (long long*)cursor, (long long)n_batches,
+                           (const int32_t*)nullptr);
 }
 
 __global__ void k_guard_global(const float* __restrict__ vals, int32_t* guard) {
@@ -812,8 +794,7 @@ __global__ void k_guard_global(const float* __restrict__ vals, int32_t* guard) {
 
 int bcnf_guard_check_global(const float* global_values, int32_t* guard, void* stream) {
   if (!global_values || !guard) return BCNF_ERR_ARG;
-  hipLaunchKernelGGL(k_guard_global, dim3(1), dim3(64), 0, (hipStream_t)stream, global_values, guard);
-  return launched();
+  return launch<k_guard_global>(dim3(1), dim3(64), 0, (hipStream_t)stream, global_values, guard);
 }
 
 int bcnf_linear_forward(const float* x, const float* weight, const float* bias, int64_t rows, int32_t in_features,
@@ -875,18 +856,14 @@ int linear_backward(const float* x, const float* weight, const float* dy, const 
     float* w = (float*)work;
     float* bw = w + (long long)splits * N * K;
     const dim3 grid((unsigned)((tiles + 3) / 4), (unsigned)splits);
-    if (sg)
-      hipLaunchKernelGGL(k_gemm_wt<true>, grid, dim3(BCNF_WG), 0, st, x, dy, (long long)rows, N, K, rps, w,
-                         dbias ? bw : nullptr, sg);
-    else
-      hipLaunchKernelGGL(k_gemm_wt<false>, grid, dim3(BCNF_WG), 0, st, x, dy, (long long)rows, N, K, rps, w,
-                         dbias ? bw : nullptr, (const float*)nullptr);
-    int rc = launched();
+    const int rc = sg ? launch<k_gemm_wt<true>>(grid, dim3(BCNF_WG), 0, st, x, dy, (long long)rows, N, K, rps, w,
+                                                dbias ? bw : nullptr, sg)
+                      : launch<k_gemm_wt<false>>(grid, dim3(BCNF_WG), 0, st, x, dy, (long long)rows, N, K, rps, w,
+                                                 dbias ? bw : nullptr, (const float*)nullptr);
     if (rc) return rc;
     const long long outs = (long long)N * K + (dbias ? N : 0);
-    hipLaunchKernelGGL(k_wt_reduce, dim3((unsigned)((outs + BCNF_WG - 1) / BCNF_WG)), dim3(BCNF_WG), 0, st, w, bw,
-                       splits, N, K, dweight, dbias);
-    return launched();
+    return launch<k_wt_reduce>(dim3((unsigned)((outs + BCNF_WG - 1) / BCNF_WG)), dim3(BCNF_WG), 0, st, w, bw, splits, N,
+                               K, dweight, dbias);
   }
   return BCNF_OK;
 }

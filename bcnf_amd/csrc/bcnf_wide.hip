@@ -38,6 +38,9 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
+using bcnf_rt::launch;
+using bcnf_rt::LDS_MAX;
+
 constexpr int WWG = 256;      // threads per workgroup of every wide kernel
 constexpr int DM = 32;        // max D of the wide family (register arrays of the link kernels)
 
@@ -1031,9 +1034,7 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS, (S * (BM + BN) * 64 * 4 <= 80 
 // 16 columns of a fragment read start on 16 distinct 4-bank groups, conflict-free). KS = 2 waves per output wave tile
 // split the chunks (contiguous halves) and meet in LDS after the loop as in tiling R (fixed order).
 // ------------------------------------------------------------------------------------------------
-#ifndef WB_P
-#define WB_P 2          // A-operand register ring depth of tiling W (chunks in flight per wave)
-#endif
+constexpr int WB_P = 2;        // A-operand register ring depth of tiling W (chunks in flight per wave)
 constexpr int WB_KMAX = 768;   // K of the resident B band (48 x 772 floats = 148 KB of LDS)
 template <int WGM, int KS, int P, int KQ, int TI = 1>
 struct WbCfg {
@@ -2009,31 +2010,21 @@ GemmArgs gemm_args(int tiling, int M, int N, int K, const float* A, long long ld
 template <int BM, int BN, int BK, bool AKC, bool BKC, int EPI>
 int launch_cfg(const GemmArgs& g, int groups, hipStream_t st) {
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, groups);
-  hipLaunchKernelGGL((k_wgemm<BM, BN, BK, AKC, BKC, EPI>), grid, dim3(WWG), 0, st, g);
-  return bcnf_rt::launched();
+  return launch<k_wgemm<BM, BN, BK, AKC, BKC, EPI>>(grid, dim3(WWG), 0, st, g);
 }
 
 template <int BM, int BN, int BK, bool AKC, bool BKC, int EPI, int NW = 4, bool FULL = false>
 int launch_cfg16(const GemmArgs& g, int groups, hipStream_t st) {
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, groups);
-  hipLaunchKernelGGL((k_wgemm16<BM, BN, BK, AKC, BKC, EPI, NW, FULL>), grid, dim3(64 * NW), 0, st, g);
-  return bcnf_rt::launched();
+  return launch<k_wgemm16<BM, BN, BK, AKC, BKC, EPI, NW, FULL>>(grid, dim3(64 * NW), 0, st, g);
 }
 
 template <int BM, int BN, int WGM, int WGN, bool AKC, bool BKC, int EPI, int S, int KS = 2>
 int launch_gl(const GemmArgs& g, int groups, hipStream_t st) {
   using T = GlCfg<BM, BN, WGM, WGN, AKC, BKC, S, KS>;
   constexpr int bytes = S * T::STG * 4;
-  static bool attr = false;
-  if (!attr) {
-    if (const int rc = bcnf_rt::hip_status(hipFuncSetAttribute((const void*)k_wgl<BM, BN, WGM, WGN, AKC, BKC, EPI, S, KS>,
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes)))
-      return rc;
-    attr = true;
-  }
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, groups);
-  hipLaunchKernelGGL((k_wgl<BM, BN, WGM, WGN, AKC, BKC, EPI, S, KS>), grid, dim3(64 * T::NW), bytes, st, g);
-  return bcnf_rt::launched();
+  return launch<k_wgl<BM, BN, WGM, WGN, AKC, BKC, EPI, S, KS>>(grid, dim3(64 * T::NW), bytes, st, g);
 }
 
 // Set by launch_wb when an EPI_ACT launch on tiling W carries GemmArgs.lp (only tiling W's epilogue writes the
@@ -2044,30 +2035,10 @@ template <int WGM, int KS, int P, int KQ, int EPI, int TI = 1>
 int launch_wb(const GemmArgs& g, int groups, hipStream_t st) {
   using T = WbCfg<WGM, KS, P, KQ, TI>;
   if (EPI == EPI_ACT && g.lp) g_lp_written = true;
-  const int bytes = T::lds_floats(g.K) * 4;
-  static bool attr = false;
-  if (!attr) {
-    if (const int rc = bcnf_rt::hip_status(hipFuncSetAttribute((const void*)k_wbr<WGM, KS, P, KQ, TI, EPI>,
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                               T::lds_floats(T::KMAX) * 4)))
-      return rc;
-    attr = true;
-  }
+  const bcnf_rt::Lds lds(T::lds_floats(g.K) * 4, T::lds_floats(T::KMAX) * 4);   // ask once, for the largest band
   dim3 grid((g.N + T::BN - 1) / T::BN, (g.M + T::BM - 1) / T::BM, groups);
-  if (g.K % T::CK == 0) {
-    static bool attr2 = false;
-    if (!attr2) {
-      if (const int rc = bcnf_rt::hip_status(hipFuncSetAttribute((const void*)k_wbr<WGM, KS, P, KQ, TI, EPI, false>,
-                                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                 T::lds_floats(T::KMAX) * 4)))
-        return rc;
-      attr2 = true;
-    }
-    hipLaunchKernelGGL((k_wbr<WGM, KS, P, KQ, TI, EPI, false>), grid, dim3(64 * T::NW), bytes, st, g);
-    return bcnf_rt::launched();
-  }
-  hipLaunchKernelGGL((k_wbr<WGM, KS, P, KQ, TI, EPI>), grid, dim3(64 * T::NW), bytes, st, g);
-  return bcnf_rt::launched();
+  return g.K % T::CK == 0 ? launch<k_wbr<WGM, KS, P, KQ, TI, EPI, false>>(grid, dim3(64 * T::NW), lds, st, g)
+                          : launch<k_wbr<WGM, KS, P, KQ, TI, EPI, true>>(grid, dim3(64 * T::NW), lds, st, g);
 }
 
 // LDS-DMA tilings per operand layout (tiling C): 5 = auto, 6 = the large-tile variant forced
@@ -2185,8 +2156,7 @@ int gemm_splitk(const GemmArgs& g, int np, float* part, long long part_floats, h
   if (rc) return rc;
   const long long n4 = (long long)g.M * (g.N / 4);
   const int grid = (int)std::min<long long>((n4 + WWG - 1) / WWG, 2048);
-  hipLaunchKernelGGL(k_wsum_parts, dim3(grid), dim3(WWG), 0, st, part, p.sC1, np, g.M, g.N / 4, ldp, g.C, g.ldc);
-  return bcnf_rt::launched();
+  return launch<k_wsum_parts>(dim3(grid), dim3(WWG), 0, st, part, p.sC1, np, g.M, g.N / 4, ldp, g.C, g.ldc);
 }
 
 // Skinny split-K Linear-gradient partials: part[g1][s][m][n] = sum_{k in split s} A[k][m] B[k][n] with one operand
@@ -2305,17 +2275,8 @@ int launch_skinny(const GemmArgs& g, int groups, int np, float* part, long long 
   const int W = WIDE_A ? g.M : g.N;
   const size_t rows = (size_t)(g.K / np);
   const size_t bytes = 4 * std::max(rows * QT, (size_t)3 * QT * 64 * 4);
-  static bool attr = false;
-  if (!attr) {
-    if (const int rc = bcnf_rt::hip_status(hipFuncSetAttribute((const void*)k_skinny<QT, WIDE_A>,
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)))
-      return rc;
-    attr = true;
-  }
-  if (bytes > 160 * 1024) return BCNF_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)((W + SK_COLS - 1) / SK_COLS), (unsigned)np, (unsigned)groups);
-  hipLaunchKernelGGL((k_skinny<QT, WIDE_A>), grid, dim3(WWG), bytes, st, g, np, part, ldp);
-  return bcnf_rt::launched();
+  return launch<k_skinny<QT, WIDE_A>>(grid, dim3(WWG), {bytes, LDS_MAX}, st, g, np, part, ldp);
 }
 
 // The skinny kernel when it applies (cost-model dispatch only; a forced tiling keeps the tiled GEMM): -1 otherwise.
@@ -2327,7 +2288,7 @@ int try_skinny(const GemmArgs& g, int groups, int np, float* part, long long ldp
   const int W = wide_a ? g.M : g.N;
   if ((ldw & 3) || (sw & 3) || ldw < ((W + 3) & ~3) || !aligned16(wide_a ? g.A : g.B) || (!wide_a && (ldp & 3)))
     return -1;
-  if ((long long)(g.K / np) * 36 * 4 > 160 * 1024) return -1;
+  if ((long long)(g.K / np) * 36 * 4 > (long long)LDS_MAX) return -1;
   const int Q = wide_a ? g.N : g.M;
   if (wide_a) {
     if (Q <= 12) return launch_skinny<12, true>(g, groups, np, part, ldp, st);
@@ -2361,9 +2322,8 @@ int lingrad_splitk(const GemmArgs& g, int groups, float* part, long long part_fl
   int rc = try_skinny(g, groups, np, part, ldp, st);       // the HBM-streaming kernel for the skinny shapes
   if (rc < 0) rc = gemm<false, false, EPI_STORE>(p, groups * np, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_wsum_lingrad, dim3((unsigned)(((long long)g.M * g.N + WWG - 1) / WWG), groups), dim3(WWG), 0, st,
-                     g, part, np, ldp);
-  return bcnf_rt::launched();
+  return launch<k_wsum_lingrad>(dim3((unsigned)(((long long)g.M * g.N + WWG - 1) / WWG), groups), dim3(WWG), 0, st, g,
+                                part, np, ldp);
 }
 
 struct WideWs {       // workspace carve-up (floats)
@@ -2411,12 +2371,14 @@ WideWs carve(const WideLayout& L, long long B, bool train, float* base) {
 
 // (tail side, head side) of a link launch -> kernel instantiation; the unused side of a head-only / tail-only
 // launch is free, so every launch maps onto (0,0) [one-way], (0,1) or (1,0) [two_way].
+// A link kernel's LDS varies with the launch (link_lds_floats): each asks for the whole of it on its first launch.
 template <bool INV, int DD>
-void link_dispatch(int ts, int hs, dim3 grid, size_t lds, hipStream_t st, const WideLayout& L, const LinkArgs& a) {
-  if (INV && a.ldj) hipLaunchKernelGGL((k_wlink<INV, DD, 0, 0, INV>), grid, dim3(WWG), lds, st, L, a);   // S == 1
-  else if (L.S == 1) hipLaunchKernelGGL((k_wlink<INV, DD, 0, 0>), grid, dim3(WWG), lds, st, L, a);
-  else if (ts == 0 && hs == 1) hipLaunchKernelGGL((k_wlink<INV, DD, 0, 1>), grid, dim3(WWG), lds, st, L, a);
-  else hipLaunchKernelGGL((k_wlink<INV, DD, 1, 0>), grid, dim3(WWG), lds, st, L, a);
+int link_dispatch(int ts, int hs, dim3 grid, size_t bytes, hipStream_t st, const WideLayout& L, const LinkArgs& a) {
+  const bcnf_rt::Lds lds(bytes, LDS_MAX);
+  return INV && a.ldj           ? launch<k_wlink<INV, DD, 0, 0, INV>>(grid, dim3(WWG), lds, st, L, a)   // S == 1
+         : L.S == 1             ? launch<k_wlink<INV, DD, 0, 0, false>>(grid, dim3(WWG), lds, st, L, a)
+         : ts == 0 && hs == 1   ? launch<k_wlink<INV, DD, 0, 1, false>>(grid, dim3(WWG), lds, st, L, a)
+                                : launch<k_wlink<INV, DD, 1, 0, false>>(grid, dim3(WWG), lds, st, L, a);
 }
 
 #ifdef BCNF_PHASE_STAMPS
@@ -2434,21 +2396,17 @@ int link_launch(const WideLayout& L, const LinkArgs& a_in, bool inv, hipStream_t
   const size_t lds = (size_t)link_lds_floats(L, a.vt >= 0, a.vh >= 0) * sizeof(float);
   const int ts = a.vt >= 0 ? a.vt % L.S : 1 - (a.vh % L.S);
   const int hs = a.vh >= 0 ? a.vh % L.S : 1 - ts;
-  if (L.D == 19) {                       // every shipped trajectory config (19 physical parameters)
-    if (inv) link_dispatch<true, 19>(ts, hs, grid, lds, st, L, a);
-    else link_dispatch<false, 19>(ts, hs, grid, lds, st, L, a);
-  } else {
-    if (inv) link_dispatch<true, 0>(ts, hs, grid, lds, st, L, a);
-    else link_dispatch<false, 0>(ts, hs, grid, lds, st, L, a);
-  }
-  return bcnf_rt::launched();
+  if (L.D == 19)                         // every shipped trajectory config (19 physical parameters)
+    return inv ? link_dispatch<true, 19>(ts, hs, grid, lds, st, L, a) : link_dispatch<false, 19>(ts, hs, grid, lds, st, L, a);
+  return inv ? link_dispatch<true, 0>(ts, hs, grid, lds, st, L, a) : link_dispatch<false, 0>(ts, hs, grid, lds, st, L, a);
 }
 
 template <int DD>
-void linkb_dispatch(int ts, int hs, dim3 grid, size_t lds, hipStream_t st, const WideLayout& L, const LinkBArgs& a) {
-  if (L.S == 1) hipLaunchKernelGGL((k_wlink_bwd<DD, 0, 0>), grid, dim3(WWG), lds, st, L, a);
-  else if (ts == 0 && hs == 1) hipLaunchKernelGGL((k_wlink_bwd<DD, 0, 1>), grid, dim3(WWG), lds, st, L, a);
-  else hipLaunchKernelGGL((k_wlink_bwd<DD, 1, 0>), grid, dim3(WWG), lds, st, L, a);
+int linkb_dispatch(int ts, int hs, dim3 grid, size_t bytes, hipStream_t st, const WideLayout& L, const LinkBArgs& a) {
+  const bcnf_rt::Lds lds(bytes, LDS_MAX);
+  return L.S == 1             ? launch<k_wlink_bwd<DD, 0, 0>>(grid, dim3(WWG), lds, st, L, a)
+         : ts == 0 && hs == 1 ? launch<k_wlink_bwd<DD, 0, 1>>(grid, dim3(WWG), lds, st, L, a)
+                              : launch<k_wlink_bwd<DD, 1, 0>>(grid, dim3(WWG), lds, st, L, a);
 }
 
 int linkb_launch(const WideLayout& L, const LinkBArgs& a, hipStream_t st) {
@@ -2456,25 +2414,7 @@ int linkb_launch(const WideLayout& L, const LinkBArgs& a, hipStream_t st) {
   const size_t lds = (size_t)link_lds_floats(L, a.vh >= 0, a.vt >= 0) * sizeof(float);
   const int ts = a.vt >= 0 ? a.vt % L.S : 1 - (a.vh % L.S);
   const int hs = a.vh >= 0 ? a.vh % L.S : 1 - ts;
-  if (L.D == 19) linkb_dispatch<19>(ts, hs, grid, lds, st, L, a);
-  else linkb_dispatch<0>(ts, hs, grid, lds, st, L, a);
-  return bcnf_rt::launched();
-}
-
-bool lds_attr_done = false;
-void ensure_lds_attrs() {
-  if (lds_attr_done) return;
-  const void* fns[] = {
-      (const void*)k_wlink<true, 0, 0, 0>,  (const void*)k_wlink<true, 0, 0, 1>,  (const void*)k_wlink<true, 0, 1, 0>,
-      (const void*)k_wlink<false, 0, 0, 0>, (const void*)k_wlink<false, 0, 0, 1>, (const void*)k_wlink<false, 0, 1, 0>,
-      (const void*)k_wlink<true, 19, 0, 0>, (const void*)k_wlink<true, 19, 0, 1>, (const void*)k_wlink<true, 19, 1, 0>,
-      (const void*)k_wlink<false, 19, 0, 0>, (const void*)k_wlink<false, 19, 0, 1>,
-      (const void*)k_wlink<false, 19, 1, 0>, (const void*)k_wlink_bwd<0, 0, 0>, (const void*)k_wlink_bwd<0, 0, 1>,
-      (const void*)k_wlink_bwd<0, 1, 0>,    (const void*)k_wlink_bwd<19, 0, 0>, (const void*)k_wlink_bwd<19, 0, 1>,
-      (const void*)k_wlink_bwd<19, 1, 0>,   (const void*)k_wlink<true, 0, 0, 0, true>,
-      (const void*)k_wlink<true, 19, 0, 0, true>};
-  for (const void* f : fns) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  lds_attr_done = true;
+  return L.D == 19 ? linkb_dispatch<19>(ts, hs, grid, lds, st, L, a) : linkb_dispatch<0>(ts, hs, grid, lds, st, L, a);
 }
 
 #define WCHK(x)            \
@@ -2489,8 +2429,7 @@ const float* padded_h(const WideLayout& L, const float* h, long long rows, float
   if (L.Cp == L.C || rows == 0) return h;
   const long long n = rows * L.Cp;
   const int grid = (int)std::min<long long>((n + WWG - 1) / WWG, 4096);
-  hipLaunchKernelGGL(k_wpad_rows, dim3(grid), dim3(WWG), 0, st, h, L.C, rows, pad, L.Cp);
-  *rc = bcnf_rt::launched();
+  *rc = launch<k_wpad_rows>(dim3(grid), dim3(WWG), 0, st, h, L.C, rows, pad, L.Cp);
   return pad;
 }
 
@@ -2565,7 +2504,6 @@ int wide_forward(const WideLayout& L, const float* prm, const float* pk, const f
                  float* z, float* ldj, bool training, const uint64_t* rng, float* ws, bool save, hipStream_t st,
                  const WideFold* fold = nullptr) {
   if (B == 0) return BCNF_OK;
-  ensure_lds_attrs();
   const bool drop = training && L.p > 0.f && rng;
   const WideWs w = carve(L, B, save, ws);
   const long long slab = B * L.HP;
@@ -2664,7 +2602,6 @@ int wide_backward(const WideLayout& L, const float* prm, const float* pk, const 
   if (B == 0) return BCNF_OK;
   if (bhi < 0) bhi = L.nb;
   if (blo < 0 || bhi > L.nb || blo >= bhi) return BCNF_ERR_ARG;
-  ensure_lds_attrs();
   const WideWs w = carve(L, B, true, ws);
   const GPlan gp = g_plan(L, B, fold && fold->dx, fold && fold->dwfb, fold ? fold->Xp : 0, blo, bhi);
   const long long gfl_all = gp.gfl_all, tail = gp.tail;
@@ -2829,9 +2766,8 @@ int wide_backward(const WideLayout& L, const float* prm, const float* pk, const 
     }
     const int an_hi = bhi < L.nb - 1 ? bhi : L.nb - 1;   // ActNorm k sits in real block k (the last block has none)
     if (L.an && an_hi > blo) {
-      hipLaunchKernelGGL(k_wactnorm_grad, dim3(an_hi - blo), dim3(WWG), 0, st, L, w.ANP, B, dldj, zn, dvals, nll, prm,
-                         dprm, blo);
-      WCHK(bcnf_rt::launched());
+      WCHK(launch<k_wactnorm_grad>(dim3(an_hi - blo), dim3(WWG), 0, st, L, w.ANP, B, dldj, zn, dvals, nll, prm, dprm,
+                                   blo));
     }
   }
   return BCNF_OK;
@@ -2846,7 +2782,6 @@ int wide_inverse(const WideLayout& L, const float* prm, const float* pk, const f
                  const int64_t* cidx, long long n, float* y, bool training, const uint64_t* rng, float* scratch,
                  hipStream_t st, float* ldj = nullptr, float* logp = nullptr) {
   if (n == 0) return BCNF_OK;
-  ensure_lds_attrs();
   const bool drop = training && L.p > 0.f && rng;
   // scratch: P (hrows x nv*HP) | A ping-pong (2 x n x HP) | X (n x XP) | padded h
   float* P = scratch;
@@ -2942,9 +2877,8 @@ int bcnf_wide_pack(const BcnfStackDesc* desc, const float* params, const float* 
   const WpackGrid g = wpack_grid(L);
   const long long nwg = g.n_tiles + g.n_rows + g.n_small;
   if (nwg > 0x7fffffffLL) return BCNF_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(k_wpack_all, dim3((unsigned)nwg), dim3(WWG), 0, (hipStream_t)stream, L, g, params, qmats,
-                     (float*)packed);
-  return bcnf_rt::launched();
+  return launch<k_wpack_all>(dim3((unsigned)nwg), dim3(WWG), 0, (hipStream_t)stream, L, g, params, qmats,
+                             (float*)packed);
 }
 
 int bcnf_wide_forward(const BcnfStackDesc* desc, const float* params, const void* packed, const float* y,
@@ -2973,9 +2907,8 @@ int bcnf_wide_nll_finalize(const BcnfStackDesc* desc, const void* workspace, int
   WCHK(wide_layout(desc, &L));
   if (batch <= 0 || !workspace || !loss_out) return BCNF_ERR_ARG;
   const WideWs w = carve(L, batch, save != 0, (float*)workspace);
-  hipLaunchKernelGGL(k_wnll_finalize, dim3(1), dim3(WWG), 0, (hipStream_t)stream, w.nllp, (long long)batch, loss_out,
-                     rng_state, guard);
-  return bcnf_rt::launched();
+  return launch<k_wnll_finalize>(dim3(1), dim3(WWG), 0, (hipStream_t)stream, w.nllp, (long long)batch, loss_out,
+                                 rng_state, guard);
 }
 
 int bcnf_wide_proj_rows(const BcnfStackDesc* desc, int64_t* rows) {
