@@ -841,15 +841,14 @@ int linear_backward(const float* x, const float* weight, const float* dy, const 
       if (const int rc = bcnf_rt::hip_status(hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)N, st))) return rc;
     return BCNF_OK;
   }
-  if (!dy) return BCNF_ERR_ARG;
+  // every refusal before the first launch: a refused call writes nothing
+  if (!dy || (dx && !weight) || ((dweight || dbias) && (!x || !work || !dweight))) return BCNF_ERR_ARG;
   if (dx) {   // dX[m][k] = sum_n dY[m][n] W[n][k]
-    if (!weight) return BCNF_ERR_ARG;
     int rc = sg ? launch_lin<false, true, false>(dy, N, weight, K, nullptr, dx, K, rows, K, N, sg, ActArgs{}, st)
                 : launch_lin<false, false, false>(dy, N, weight, K, nullptr, dx, K, rows, K, N, nullptr, ActArgs{}, st);
     if (rc) return rc;
   }
-  if (dweight || dbias) {
-    if (!x || !work || !dweight) return BCNF_ERR_ARG;
+  if (dweight) {
     const int rps = split_rows(rows);
     const int splits = (int)((rows + rps - 1) / rps);
     const int tiles = ((N + 15) / 16) * ((K + 15) / 16);

@@ -345,7 +345,8 @@ int bcnf_linear_forward(const float* x, const float* weight, const float* bias, 
 /* Scratch bytes bcnf_linear_backward needs for its split-K weight gradient. */
 int64_t bcnf_linear_work_bytes(int64_t rows, int32_t in_features, int32_t out_features);
 /* dx (nullable) = dy W; dweight = dy^T x and dbias (nullable) = column sums of dy, both overwritten
- * (fixed-order split-K reduction through `work`). dweight may be NULL only when dbias is NULL too. */
+ * (fixed-order split-K reduction through `work`). dweight may be NULL only when dbias is NULL too. A refused call
+ * (BCNF_ERR_ARG) launches nothing; rows = 0 zero-fills dweight and dbias. */
 int bcnf_linear_backward(const float* x, const float* weight, const float* dy, int64_t rows, int32_t in_features,
                          int32_t out_features, float* dx, float* dweight, float* dbias, void* work, void* stream);
 /* One hidden layer of a FullyConnectedFeatureNetwork, nn.Linear -> nn.GELU() -> nn.Dropout(p) (feature_network.py:

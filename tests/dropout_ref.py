@@ -4,7 +4,8 @@ Not the reference's RNG: the reference draws nn.Dropout masks with torch's gener
 in-kernel generator can reproduce, so training parity is gated against the fp64 oracle fed the kernels' own masks
 (keep_callable below hands them over). This module pins the kernel's own stream bit for bit:
 Philox4x32-10 (Salmon et al. 2011, checked against the Random123 known-answer vectors in tests/test_dropout_rule.py)
-and the keep rule "u32 >= round(p 2^32)".
+and the keep rule "u32 >= round(p 2^32)". feature_keep restates the feature-MLP layers' draw (k_lin / k_gemm) the same
+way, for the fp64 oracle of tests/test_gpu_linear.py.
 """
 import numpy as np
 
@@ -81,6 +82,21 @@ def keep_callable(p, seed, offset, n_blocks, hidden, batch, tag=0):
         assert half == "a" and 0 <= k < n_blocks and 0 <= li < len(hidden)
         return torch.from_numpy(((bits[k, :, :hidden[li]] >> np.uint32(li)) & np.uint32(1)).astype(bool))
     return keep
+
+
+def feature_keep(p, seed, offset, salt, rows, cols):
+    """bool [rows, cols] keep mask of one fused feature layer (bcnf_train.hip: the ACT epilogue of k_lin / k_gemm,
+    bcnf_linear_gelu_forward): unit (row, column) is word row & 3 of the draw with counter (column, row >> 2, offset
+    low, offset high) and key (seed low ^ salt 0x9E3779B9, seed high ^ 0x80000000); keep iff u32 >= thresh32(p)."""
+    seed, offset = int(seed) & (2**64 - 1), int(offset) & (2**64 - 1)
+    k0 = (seed & 0xFFFFFFFF) ^ (((int(salt) & 0xFFFFFFFF) * 0x9E3779B9) & 0xFFFFFFFF)
+    k1 = ((seed >> 32) ^ 0x80000000) & 0xFFFFFFFF
+    quads = (rows + 3) // 4
+    col = np.arange(cols, dtype=np.uint64)[None, :]
+    quad = np.arange(quads, dtype=np.uint64)[:, None]
+    words = philox4x32_10(col, quad, offset & 0xFFFFFFFF, offset >> 32, k0, k1)      # four [quads, cols]
+    u = np.stack([np.broadcast_to(w, (quads, cols)) for w in words], axis=1).reshape(4 * quads, cols)[:rows]
+    return u >= np.uint64(thresh32(p))
 
 
 # The small-family (register-resident k_forward / k_backward / k_inverse) shapes the training-parity tests use besides

@@ -1,11 +1,13 @@
 """CPU checks of the FC_small kernels' dropout rule as restated in tests/dropout_ref.py (the GPU kernels are checked
 bit for bit against it in tests/test_gpu_dropout.py): Philox4x32-10 against the Random123 known-answer vectors, and
 the keep rule's effective p equal to nn.Dropout's p (cnf.py:82-83) to 2^-32 at every p, including p < 2^-17, which
-round 5's 16-bit rule ran as no dropout at all."""
+round 5's 16-bit rule ran as no dropout at all. The feature layers' draw (feature_keep; the GPU kernels against it
+in tests/test_gpu_linear.py): its counter / key layout unit by unit, p = 0, the keep rate, and that the salt and both
+halves of the offset reach the draw."""
 import numpy as np
 import pytest
 
-from dropout_ref import keep_bits, philox4x32_10, thresh32
+from dropout_ref import feature_keep, keep_bits, philox4x32_10, thresh32
 
 
 @pytest.mark.parametrize("ctr,key,out", [
@@ -44,3 +46,45 @@ def test_keep_rule_statistics():
     n = 8 * 8 * s.size
     lam = 1e-6 * n
     assert drops > 0 and abs(drops - lam) < 4 * np.sqrt(lam), (drops, lam)
+
+
+FEATURE_STATE = (0x123456789ABCDEF, 2**32 + 5)           # (seed, offset): both halves of both nonzero
+
+
+def test_feature_keep_layout_unit_by_unit():
+    """The vectorised mask against the rule written out per unit: counter (column, row >> 2, offset low, offset
+    high), key (seed low ^ salt 0x9E3779B9, seed high ^ 0x80000000), word row & 3."""
+    seed, offset = FEATURE_STATE
+    p, salt, rows, cols = 0.3, 6, 11, 5
+    got = feature_keep(p, seed, offset, salt, rows, cols)
+    assert got.shape == (rows, cols) and got.dtype == np.bool_
+    k0 = (seed & 0xFFFFFFFF) ^ ((salt * 0x9E3779B9) & 0xFFFFFFFF)
+    k1 = (seed >> 32) ^ 0x80000000
+    for r in range(rows):
+        for c in range(cols):
+            w = philox4x32_10(c, r >> 2, offset & 0xFFFFFFFF, offset >> 32, k0, k1)
+            assert bool(got[r, c]) == (int(w[r & 3]) >= thresh32(p)), (r, c)
+
+
+def test_feature_keep_p0_keeps_everything():
+    assert feature_keep(0.0, *FEATURE_STATE, 3, 37, 33).all()
+
+
+@pytest.mark.parametrize("p", [0.111, 0.5])
+def test_feature_keep_rate(p):
+    keep = feature_keep(p, *FEATURE_STATE, 3, 1024, 1024)          # 2^20 units
+    n, q = keep.size, 1.0 - thresh32(p) / 2**32
+    assert n >= 10**6
+    assert abs(keep.mean() - q) < 4 * np.sqrt(q * (1 - q) / n), (keep.mean(), q)
+
+
+def test_feature_keep_salt_and_offset_halves_reach_the_draw():
+    seed, offset = FEATURE_STATE
+    base = feature_keep(0.5, seed, offset, 3, 64, 64)
+    assert np.array_equal(base, feature_keep(0.5, seed, offset, 3, 64, 64))
+    for other in (feature_keep(0.5, seed, offset, 4, 64, 64),              # salt
+                  feature_keep(0.5, seed, offset + 1, 3, 64, 64),          # offset, low half
+                  feature_keep(0.5, seed, offset + 2**32, 3, 64, 64),      # offset, high half
+                  feature_keep(0.5, seed ^ 1, offset, 3, 64, 64),          # seed, low half
+                  feature_keep(0.5, seed ^ 2**32, offset, 3, 64, 64)):     # seed, high half
+        assert 0.4 < (other != base).mean() < 0.6                          # an independent draw, not a shift

@@ -10,13 +10,10 @@ import pytest
 import torch
 
 from conftest import close, golden_sd, load_golden
+from gpu_guard import DEV, canaries_alive, guarded
 from test_transformer_cpu import MODEL_CFG, T1, build
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-GUARD = 64
-NAN = float("nan")
 
 
 @pytest.fixture(scope="module")
@@ -26,25 +23,6 @@ def g16():
 
 def t(a):
     return torch.from_numpy(a).to(DEV)
-
-
-def guarded(rows, width, ld=None, data=None):
-    """(buffer, view): a (rows, width) view with row stride ld inside a NaN-filled buffer with GUARD floats either
-    side; `data` is copied into the view, everything else stays NaN."""
-    ld = width if ld is None else ld
-    buf = torch.full((2 * GUARD + rows * ld,), NAN, dtype=torch.float32, device=DEV)
-    view = buf[GUARD:GUARD + rows * ld].view(rows, ld)[:, :width]
-    if data is not None:
-        view.copy_(data)
-    return buf, view
-
-
-def canaries_alive(buf, rows, width, ld=None):
-    ld = width if ld is None else ld
-    outside = torch.ones_like(buf, dtype=torch.bool)
-    outside[GUARD:GUARD + rows * ld].view(rows, ld)[:, :width] = False
-    inside = buf[~outside]
-    return bool(torch.isnan(buf[outside]).all()) and bool(torch.isfinite(inside).all())
 
 
 # ------------------------------------------------------------------------------------------ attention core
