@@ -105,7 +105,7 @@ __global__ __launch_bounds__(BCNF_WG) void k_adam(TList T, const float* __restri
         t[q][e] = t0;
         o[q][e] = o0 + e;
       }
-    } else {
+    } else if (total > 0) {   // an empty set has no element to clamp to: nothing is loaded (or used)
 #pragma unroll
       for (int e = 0; e < EPT; ++e) {
         long long i = i0[q] + e;
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(BCNF_WG) void k_clip(TList T, const float* __restri
         t[q][e] = t0;
         o[q][e] = o0 + e;
       }
-    } else {
+    } else if (total > 0) {   // as in k_adam
 #pragma unroll
       for (int e = 0; e < EPT; ++e) {
         long long i = i0[q] + e;
@@ -597,7 +597,7 @@ int make_tlist(int n, float* const* p, float* const* g, float* const* m, float* 
   T->n = n;
   T->start[0] = 0;
   for (int i = 0; i < n; ++i) {
-    if (numel[i] < 0 || !g[i]) return BCNF_ERR_ARG;
+    if (numel[i] < 0 || (!g[i] && numel[i] > 0)) return BCNF_ERR_ARG;   // an empty tensor's pointer may be NULL
     T->p[i] = p ? p[i] : nullptr;
     T->g[i] = g[i];
     T->m[i] = m ? m[i] : nullptr;
@@ -679,7 +679,7 @@ int bcnf_adam_step(int32_t n_tensors, float* const* params, float* const* grads,
   if (rc) return rc;
   if (!params || !exp_avg || !exp_avg_sq || !step) return BCNF_ERR_ARG;
   for (int i = 0; i < n_tensors; ++i)
-    if (!T.p[i] || !T.m[i] || !T.v[i]) return BCNF_ERR_ARG;
+    if (numel[i] > 0 && (!T.p[i] || !T.m[i] || !T.v[i])) return BCNF_ERR_ARG;
   const long long total = T.start[T.n];
   const unsigned nwg = (unsigned)n_partials(total);
   hipStream_t st = (hipStream_t)stream;
@@ -702,7 +702,7 @@ int bcnf_adam_step_bookkeep(int32_t n_tensors, float* const* params, float* cons
   if (!params || !exp_avg || !exp_avg_sq || !step || !done_counter) return BCNF_ERR_ARG;
   if (advance_cursor && cursor_modulo < 1) return BCNF_ERR_ARG;
   for (int i = 0; i < n_tensors; ++i)
-    if (!T.p[i] || !T.m[i] || !T.v[i]) return BCNF_ERR_ARG;
+    if (numel[i] > 0 && (!T.p[i] || !T.m[i] || !T.v[i])) return BCNF_ERR_ARG;
   const long long total = T.start[T.n];
   const unsigned nwg = (unsigned)n_partials(total);
   const AdamBook bk{step, (long long*)advance_cursor, (long long)cursor_modulo, log_values, log_history,

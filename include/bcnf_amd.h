@@ -264,7 +264,12 @@ int bcnf_nll_backward(const BcnfStackDesc* desc, const void* packed, const float
 /* ---- Optimizer ------------------------------------------------------------------------------------
  * Tensors are passed as arrays of n_tensors (<= BCNF_MAX_TENSORS) device pointers + element counts and
  * treated as one concatenated index space. bcnf_grad_partials(total) = floats of the partials buffer the kernels
- * below write / read: one sum of squared gradients per workgroup, plus one slot for their pre-reduced total. */
+ * below write / read: one sum of squared gradients per workgroup, plus one slot for their pre-reduced total.
+ * Empty tensors: the pointer arrays are required, but the pointer of a tensor with numel[i] == 0 may be NULL (what
+ * torch gives as an empty tensor's data pointer); such a tensor takes no part. A set whose total is 0 still runs
+ * its one workgroup, which forms no address into any tensor (the kernels' clamped-index loads are skipped when
+ * there is no element to clamp to): partial 0 and the total norm are 0, and the step count, cursor and log
+ * bookkeeping happen as for any other set. */
 int64_t bcnf_grad_partials(int64_t total_numel);
 
 /* One torch.optim.Adam step (amsgrad = maximize = False) over every tensor; hyper-parameters are
