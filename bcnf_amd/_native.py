@@ -34,6 +34,7 @@ EXPORTS = (
     "bcnf_inverse_scratch_bytes", "bcnf_stack_dh", "bcnf_backward_tail", "bcnf_gather_rows2",
     "bcnf_gather_batch", "bcnf_advance_counters", "bcnf_fold_bytes", "bcnf_fold_slab_bytes",
     "bcnf_pack_params_fold", "bcnf_fold_nll_forward", "bcnf_fold_backward_tail",
+    "bcnf_fold_tail_plan",
     "bcnf_fold_raw_table_bytes", "bcnf_fold_raw_table", "bcnf_fold_train_forward", "bcnf_lds_fill",
     "bcnf_wide_supported", "bcnf_wide_param_count", "bcnf_wide_packed_bytes", "bcnf_wide_workspace_bytes", "bcnf_wide_inverse_scratch_bytes",
     "bcnf_wide_pack", "bcnf_wide_forward", "bcnf_wide_nll_finalize", "bcnf_wide_backward", "bcnf_wide_inverse",
@@ -161,6 +162,7 @@ def _bind(lib):
                                            _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
         "bcnf_fold_backward_tail": (_i32, [_pdesc, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp,
                                            _vp, _vp, _vp]),
+        "bcnf_fold_tail_plan": (_i32, [_pdesc, _i32, _i64, _pi64]),
         "bcnf_grad_partials": (_i64, [_i64]),
         "bcnf_adam_step": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _i32, _vp, _vp]),

@@ -1139,6 +1139,29 @@ __global__ __launch_bounds__(BCNF_WG) void k_fold_gx(long long total, const floa
   gx_reduce_body(total, work, splits, gx, (long long)blockIdx.x * BCNF_WG + threadIdx.x);
 }
 
+// The slab reduce of the folded tail (reduce_body, below) is cut into contiguous ranges of its workgroups, one per
+// launch that takes a share (fold_tail_plan: k_fold_tail and k_fold_finish): the launch's own workgroups come first
+// in its grid, block indices past them (`own`) run reduce workgroups first, first + 1, ... k_fold_finish is
+// latency-bound and leaves the memory system nearly idle; the slab stream is the tail's only bandwidth-bound work.
+// No hand-off: nothing a reduce workgroup reads is written by its launch, and what it writes (dparams and the Adam
+// state outside the W1 condition columns) no other role touches.
+struct RedShare {
+  const float* slab;
+  long long stride;     // slab_stride_of
+  int nwg;              // slabs (backward workgroups)
+  int own, first;       // the launch's own workgroups; the first reduce workgroup of its share
+  float* dparams;
+};
+// Where a reduce workgroup's Adam scalars come from (compile-time): no Adam; derived from the step count inside the
+// workgroup (k_fold_tail only: nothing of that launch writes the count); or the two floats k_fold_tail's publisher
+// workgroup stored (adam_scalars_publish, the same double arithmetic, so the update is bit-identical), loaded with the
+// other operands as k_fold_finish's own roles load them -- k_fold_finish's share, which must not read the step count:
+// the keeper thread of that launch advances it at its end.
+enum RedAdam { RED_NO_ADAM, RED_ADAM_DERIVED, RED_ADAM_PUBLISHED };
+template <RedAdam AM>
+__device__ __forceinline__ void reduce_share(const BcnfLayout& L, const RedShare& R, const FoldAdamArgs& A,
+                                             float* __restrict__ smem);
+
 // Folded path, last launch of the backward: two small GEMMs as 16 x 16 output tiles, each operand K-chunk staged
 // in LDS as [k][16] in one memory round trip (every load of a chunk issued together: the operands were written by
 // other XCDs, so each access is an L2 miss and a streaming K loop of dependent round trips is what costs).
@@ -1149,6 +1172,9 @@ __global__ __launch_bounds__(BCNF_WG) void k_fold_gx(long long total, const floa
 // k-slices are summed in a fixed order through LDS.
 // wf / bf are k_fold_tail's copy of the feature Linear in the tail's scratch, not the parameters: role b's fused
 // Adam updates those in place in this launch, and nothing orders role a's reads before it.
+// Behind the two roles' workgroups the grid carries this launch's share of the slab reduce (RedShare): every
+// workgroup of the launch has the 64 KB of LDS, two per CU, so 512 slots for the 190 finish workgroups of FC_small
+// plus the share.
 __device__ __forceinline__ int c0_of_finish(int bx, int nct) { return (bx % nct) * 16; }
 
 constexpr int FIN_KC = 512;                           // K chunk: role a (Xp <= 256) and role b at nb <= 32
@@ -1188,8 +1214,12 @@ __global__ __launch_bounds__(BCNF_WG) void k_fold_finish(BcnfLayout L, const flo
                                                          const float* __restrict__ gx, const float* __restrict__ wf,
                                                          const float* __restrict__ bf, int X,
                                                          float* __restrict__ dparams, float* __restrict__ dwf,
-                                                         float* __restrict__ dbf, FoldAdamArgs A) {
+                                                         float* __restrict__ dbf, FoldAdamArgs A, RedShare R) {
   extern __shared__ __attribute__((aligned(16))) float smem[];   // FIN_SMEM floats (64 KB: dynamic)
+  if ((int)blockIdx.x >= R.own) {                      // this launch's share of the slab reduce (RedShare)
+    reduce_share<RED_ADAM_PUBLISHED>(L, R, A, smem);
+    return;
+  }
   float* As = smem;
   float* Bs = smem + FIN_KC * 16;
   const int Xp = fold_xp(X), tid = threadIdx.x, nct = L.Cp >> 4;
@@ -2905,6 +2935,8 @@ constexpr int RED_G = 8, RED_O4 = 32, RED_T = 16;
 // first load).
 constexpr int RED_SMEM = RED_G * RED_O4 * 4 + 4;      // floats: the partial sums, then the two scalars
 
+// AM (RedAdam, above k_fold_finish): where the Adam scalars come from.
+template <RedAdam AM>
 __device__ __forceinline__ void reduce_body(const BcnfLayout& L, const float* __restrict__ slab, long long stride,
                                             int nwg, float* __restrict__ out, int bx, float* __restrict__ smem,
                                             const FoldAdamArgs* A = nullptr) {
@@ -2917,18 +2949,23 @@ __device__ __forceinline__ void reduce_body(const BcnfLayout& L, const float* __
   const int m = (int)(ic / L.sblk), o = (int)(ic - (long long)m * L.sblk);
   long long ci[4];
   float ap[4], am[4], av[4];
-  const float step0 = A ? A->step[0] : 0.f;
+  const float step0 = AM == RED_ADAM_DERIVED ? A->step[0] : 0.f;
+  float pub[2] = {0.f, 0.f};
+  if (AM == RED_ADAM_PUBLISHED && g == 0) {
+    pub[0] = A->asc[0];
+    pub[1] = A->asc[1];
+  }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     ci[e] = slab_to_canonical(L, m, o + e);
-    if (A && g == 0) {
+    if (AM != RED_NO_ADAM && g == 0) {
       const long long c = ci[e] >= 0 ? ci[e] : 0;
       ap[e] = A->p[0][c];
       am[e] = A->m[0][c];
       av[e] = A->v[0][c];
     }
   }
-  bool scalars_due = A != nullptr;
+  bool scalars_due = AM == RED_ADAM_DERIVED;
   auto scalars = [&]() {
     const double t = (double)(step0 + 1.0f);
     if (threadIdx.x == 0) sc[0] = (float)(A->lr / (1.0 - pow(A->b1, t)));
@@ -2955,18 +2992,32 @@ __device__ __forceinline__ void reduce_body(const BcnfLayout& L, const float* __
 #pragma unroll
   for (int q = 1; q < RED_G; ++q) tot += part[q][o4];
   AdamScalars as{};
-  if (A) as = adam_scalars_of(*A, sc[0], sc[1]);
+  if (AM == RED_ADAM_DERIVED) as = adam_scalars_of(*A, sc[0], sc[1]);
+  if (AM == RED_ADAM_PUBLISHED) as = adam_scalars_of(*A, pub[0], pub[1]);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     if (ci[e] < 0) continue;
     out[ci[e]] = tot[e];
-    if (A) {
+    if (AM != RED_NO_ADAM) {
       adam_elem(ap[e], tot[e], am[e], av[e], as);
       A->p[0][ci[e]] = ap[e];
       A->m[0][ci[e]] = am[e];
       A->v[0][ci[e]] = av[e];
     }
   }
+}
+
+// A reduce workgroup of k_fold_tail or k_fold_finish (block indices past the launch's own workgroups; a
+// workgroup-uniform branch of the caller). Per output element the same reduce_body whichever launch runs it.
+template <RedAdam AM>
+__device__ __forceinline__ void reduce_share(const BcnfLayout& L, const RedShare& R, const FoldAdamArgs& A,
+                                             float* __restrict__ smem) {
+  const int bx = R.first + ((int)blockIdx.x - R.own);
+  if (A.on && !(A.guard && A.guard[BCNF_GUARD_HALTED])) {      // (a halted step updates nothing)
+    reduce_body<AM>(L, R.slab, R.stride, R.nwg, R.dparams, bx, smem, &A);
+    return;
+  }
+  reduce_body<RED_NO_ADAM>(L, R.slab, R.stride, R.nwg, R.dparams, bx, smem);
 }
 
 // The backward's tail in ONE launch: dL/dh tiles, the slab reduction and the W1 condition-part split-K
@@ -2993,7 +3044,7 @@ __global__ __launch_bounds__(BCNF_WG) void k_bwd_tail(BcnfLayout L, TailGrid G, 
   }
   i -= G.n_dh;
   if (i < G.n_red) {
-    reduce_body(L, slab, stride, nwg, dparams, i, smem);
+    reduce_body<RED_NO_ADAM>(L, slab, stride, nwg, dparams, i, smem);
     return;
   }
   i -= G.n_red;
@@ -3007,7 +3058,9 @@ __global__ __launch_bounds__(BCNF_WG) void k_bwd_tail(BcnfLayout L, TailGrid G, 
 //               reduce fills the machine behind them;
 //   n_sk        one workgroup: copies [Wf | bf] into the tail's scratch for k_fold_finish (which Adam-updates the
 //               tensors themselves) and publishes the step's Adam scalars for it;
-//   the rest    slab reduce (reduce_body), with the fused Adam's scalars derived in each workgroup.
+//   the rest    slab reduce (reduce_body) of this launch's share of the reduce workgroups (fold_tail_plan: the other
+//               share runs behind k_fold_finish's own workgroups), with the fused Adam's scalars derived in each
+//               workgroup.
 // The order is for speed only: no role reads what another role of this launch writes.
 // An earlier one-launch tail (r01j) measured 28 us against 13 + 10 for two launches, for two reasons that were not
 // the overlap itself: its grid put the split-K last, so the latency-bound role ran alone at the end, and every
@@ -3017,8 +3070,7 @@ template <bool VEC, int NT>
 __global__ __launch_bounds__(BCNF_WG, VEC && NT <= 3 ? 4 : 2) void k_fold_tail(BcnfLayout L, BcnfLayout F, const float* __restrict__ d1,
                                                        const float* __restrict__ x, long long B, int rows_per_split,
                                                        float* __restrict__ work, int gx_dw, int n_sk, int ones,
-                                                       const float* __restrict__ slab, long long stride, int nwg,
-                                                       float* __restrict__ dparams, const float* __restrict__ wf,
+                                                       RedShare R, const float* __restrict__ wf,
                                                        const float* __restrict__ bf, float* __restrict__ wf1,
                                                        FoldAdamArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -3045,11 +3097,7 @@ __global__ __launch_bounds__(BCNF_WG, VEC && NT <= 3 ? 4 : 2) void k_fold_tail(B
     if (A.on && threadIdx.x == 0) adam_scalars_publish(A);
     return;
   }
-  if (A.on && !(A.guard && A.guard[BCNF_GUARD_HALTED])) {      // (a halted step updates nothing)
-    reduce_body(L, slab, stride, nwg, dparams, bx - n_sk - 1, smem, &A);
-    return;
-  }
-  reduce_body(L, slab, stride, nwg, dparams, bx - n_sk - 1, smem);
+  reduce_share<RED_ADAM_DERIVED>(L, R, A, smem);
 }
 
 // Test hook: the whole dynamic LDS of the workgroup set to `value` (bcnf_lds_fill).
@@ -3474,6 +3522,52 @@ int bcnf_fold_train_forward(const BcnfStackDesc* desc, const float* params, cons
                       true, finalize != 0, loss_out, guard, stream, nullptr, 0, 0, &R);
 }
 
+// The folded tail's three launches (host arithmetic only; bcnf_fold_tail_plan reports it): each launch's own
+// workgroups, and the contiguous range [first, first + count) of the n_red slab-reduce workgroups that runs behind
+// them (RedShare). k_fold_finish takes a fixed quarter of n_red, rounded down, from the high end; k_fold_tail keeps
+// the rest, so a stack with fewer reduce workgroups than launches is still covered. k_fold_gx takes none: a reduce
+// workgroup lasts about twice that launch.
+constexpr int FOLD_RED_FIN_8THS = 2;
+struct FoldTailPlan {
+  long long S, splits;  // slab stride (floats); split-K splits
+  int n_red, gx_dw;
+  int own[3];           // own workgroups of k_fold_tail (split-K + the copy workgroup), k_fold_gx, k_fold_finish
+  int first[3], count[3];
+};
+FoldTailPlan fold_tail_plan(const BcnfLayout& L, const BcnfLayout& F, int64_t batch) {
+  FoldTailPlan P;
+  P.S = slab_stride_of(L);
+  P.splits = w1h_splits(batch);
+  P.n_red = (int)((P.S / 4 + RED_O4 - 1) / RED_O4);
+  P.gx_dw = (L.nb + 1) / 2;
+  P.own[0] = (int)(P.gx_dw * P.splits) + 1;
+  P.own[1] = (int)(((long long)L.nb * 16 * F.Cp + BCNF_WG - 1) / BCNF_WG);
+  P.own[2] = (L.nb + (F.Cp >> 4)) * (L.Cp >> 4);
+  P.count[1] = 0;
+  P.count[2] = (int)((long long)P.n_red * FOLD_RED_FIN_8THS / 8);
+  P.count[0] = P.n_red - P.count[2];
+  P.first[0] = 0;
+  P.first[1] = P.first[2] = P.count[0];
+  return P;
+}
+
+int bcnf_fold_tail_plan(const BcnfStackDesc* desc, int32_t in_features, int64_t batch, int64_t* out) {
+  BcnfLayout L;
+  const int rc = fold_setup(desc, in_features, &L);
+  if (rc) return rc;
+  if (!out || batch < 1) return BCNF_ERR_ARG;
+  const FoldTailPlan P = fold_tail_plan(L, fold_layout(L, in_features, in_features), batch);
+  out[0] = P.n_red;
+  out[1] = P.S;
+  for (int t = 0; t < 3; ++t) {
+    out[2 + 2 * t] = P.first[t];
+    out[3 + 2 * t] = P.count[t];
+    out[8 + t] = P.own[t] + P.count[t];
+    out[11 + t] = P.own[t];
+  }
+  return BCNF_OK;
+}
+
 int bcnf_fold_backward_tail(const BcnfStackDesc* desc, const void* packed, const void* slab, const float* x,
                             int32_t ldx, int32_t in_features, const float* feat_weight, const float* feat_bias,
                             const void* workspace, int64_t batch, int32_t training, float* dparams,
@@ -3512,38 +3606,39 @@ int bcnf_fold_backward_tail(const BcnfStackDesc* desc, const void* packed, const
   }
   const BcnfLayout F = fold_layout(L, in_features, ldx);
   hipStream_t st = (hipStream_t)stream;
-  const long long S = slab_stride_of(L);
+  const FoldTailPlan P = fold_tail_plan(L, F, batch);
+  const long long S = P.S;
   const int nwg = (int)((batch + 15) / 16);
   const float* d1 = (const float*)workspace + ws_d1_off(L, batch);
   float* work = (float*)slab + (long long)nwg * S;
   float* gx = work + w1h_work_floats(F, batch);
   A.asc = gx + (long long)L.nb * 16 * F.Cp;
   const int rps = W1H_ROWS_PER_SPLIT;
-  const long long splits = w1h_splits(batch);
   float* wf1 = A.asc + 4;                              // [Wf | bf] as k_fold_finish's role a reads them
   const float* bf1 = feat_bias ? wf1 + (long long)L.C * in_features : nullptr;
-  const int n_red = (int)((S / 4 + RED_O4 - 1) / RED_O4);
-  const int gx_dw = (L.nb + 1) / 2;
-  const long long n_sk = (long long)gx_dw * splits;
-  const dim3 grid((unsigned)(n_sk + 1 + n_red));
+  RedShare R[3];
+  unsigned grid[3];
+  for (int t = 0; t < 3; ++t) {
+    R[t] = RedShare{(const float*)slab, S, nwg, P.own[t], P.first[t], dparams};
+    grid[t] = (unsigned)(P.own[t] + P.count[t]);
+  }
+  const int n_sk = P.own[0] - 1;
   size_t lds = dw1h_half_lds_bytes(F);
   if (lds < sizeof(float) * RED_SMEM) lds = sizeof(float) * RED_SMEM;
   const bool vec = vec_rows(F, x);
   const bool nt3 = (F.Cp >> 4) <= 6;                   // column tiles per wave: 3 (Xp <= 96: FC_small) or 8
 #define FOLD_TAIL(V, NT)                                                                                          \
-  launch<k_fold_tail<V, NT>>(grid, dim3(BCNF_WG), lds, st, L, F, d1, x, (long long)batch, rps, work, gx_dw, (int)n_sk, \
-                             (int)in_features, (const float*)slab, S, nwg, dparams, feat_weight, feat_bias, wf1, A)
+  launch<k_fold_tail<V, NT>>(dim3(grid[0]), dim3(BCNF_WG), lds, st, L, F, d1, x, (long long)batch, rps, work, P.gx_dw, \
+                             n_sk, (int)in_features, R[0], feat_weight, feat_bias, wf1, A)
   rc = vec ? (nt3 ? FOLD_TAIL(true, 3) : FOLD_TAIL(true, 8)) : (nt3 ? FOLD_TAIL(false, 3) : FOLD_TAIL(false, 8));
 #undef FOLD_TAIL
   if (rc) return rc;
   const long long total = (long long)L.nb * 16 * F.Cp;
-  rc = launch<k_fold_gx>(dim3((unsigned)((total + BCNF_WG - 1) / BCNF_WG)), dim3(BCNF_WG), 0, st, total,
-                         (const float*)work, (int)splits, gx);
+  rc = launch<k_fold_gx>(dim3(grid[1]), dim3(BCNF_WG), 0, st, total, (const float*)work, (int)P.splits, gx);
   if (rc) return rc;
-  const int n_fin = (L.nb + (F.Cp >> 4)) * (L.Cp >> 4);
-  return launch<k_fold_finish>(dim3((unsigned)n_fin), dim3(BCNF_WG), sizeof(float) * FIN_SMEM, st, L,
+  return launch<k_fold_finish>(dim3(grid[2]), dim3(BCNF_WG), sizeof(float) * FIN_SMEM, st, L,
                                (const float*)packed, (const float*)gx, (const float*)wf1, bf1, (int)in_features,
-                               dparams, dfeat_weight, dfeat_bias, A);
+                               dparams, dfeat_weight, dfeat_bias, A, R[2]);
 }
 
 int bcnf_grad_reduce(const BcnfStackDesc* desc, const void* slab, const float* h, const void* workspace,

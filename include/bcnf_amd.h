@@ -211,6 +211,14 @@ int bcnf_fold_backward_tail(const BcnfStackDesc* desc, const void* packed, const
                             const void* workspace, int64_t batch, int32_t training, float* dparams,
                             float* dfeat_weight, float* dfeat_bias, const BcnfFoldAdam* adam /* nullable */,
                             void* stream);
+/* Test hook (host arithmetic only, no launch): how one bcnf_fold_backward_tail call at `batch` rows spreads its slab
+ * reduce over its three launches (k_fold_tail, k_fold_gx, k_fold_finish; the call computes its grids from the same
+ * function). The reduce has n_red workgroups of 128 slab floats each over the slab stride S; each launch runs its own
+ * workgroups first, then one contiguous range of the reduce workgroups (k_fold_gx's range is empty: DESIGN.md 7).
+ * out[0] = n_red, out[1] = S (floats), out[2 + 2t] / out[3 + 2t] = first / count of launch t's range (t = 0, 1, 2 in
+ * launch order; a count may be 0), out[8 + t] = launch t's grid size, out[11 + t] = its own workgroups (grid -
+ * count). `out`: 14 int64. Checked by tests/test_fold_tail_plan.py. */
+int bcnf_fold_tail_plan(const BcnfStackDesc* desc, int32_t in_features, int64_t batch, int64_t* out);
 
 /* Deterministic (fixed-order) reduction of a backward's gradient scratch into dparams, including the
  * W1 condition columns (split-K GEMM of D1 with h). Replaces autograd's implicit batch reduction. */
