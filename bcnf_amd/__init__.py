@@ -5,8 +5,9 @@ forward / inverse / sample API and state_dict layout, with the coupling stack on
 """
 from bcnf_amd.cnf import (ActNorm, CondRealNVP_v2, ConditionalAffineCouplingLayer, ConditionalInvertibleLayer,
                           ConditionalNestedNeuralNetwork, InvertibleLayer, OrthonormalTransformation)
-from bcnf_amd.feature_network import (ConcatenateCondition, DualDomainTransformer, FeatureNetwork, FeatureNetworkStack,
-                                      FullyConnectedFeatureNetwork, LSTMFeatureNetwork, Transformer)
+from bcnf_amd.feature_network import (ConcatenateCondition, DualDomainLSTM, DualDomainTransformer, FeatureNetwork,
+                                      FeatureNetworkStack, FullyConnectedFeatureNetwork, LSTMFeatureNetwork,
+                                      Transformer, VerboseLSTM)
 from bcnf_amd.sampling import posterior_mode
 from bcnf_amd.utils import ParameterIndexMapping, inn_nll_loss, load_config, log_prob_from_latent
 
@@ -14,7 +15,7 @@ __all__ = [
     "ActNorm", "CondRealNVP_v2", "ConditionalAffineCouplingLayer", "ConditionalInvertibleLayer",
     "ConditionalNestedNeuralNetwork", "InvertibleLayer", "OrthonormalTransformation", "ConcatenateCondition",
     "FeatureNetwork", "FeatureNetworkStack", "FullyConnectedFeatureNetwork", "LSTMFeatureNetwork",
-    "Transformer", "DualDomainTransformer",
+    "Transformer", "DualDomainTransformer", "VerboseLSTM", "DualDomainLSTM",
     "ParameterIndexMapping", "inn_nll_loss", "load_config", "log_prob_from_latent",
     "posterior_mode",
 ]

@@ -46,6 +46,7 @@ EXPORTS = (
     "bcnf_stack_inverse_logdet", "bcnf_wide_inverse_logdet",
     "bcnf_attn_forward", "bcnf_attn_backward", "bcnf_add_layernorm_forward", "bcnf_add_layernorm_work_bytes",
     "bcnf_add_layernorm_backward",
+    "bcnf_lstm_forward", "bcnf_lstm_backward",
 )
 ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
 MAX_TENSORS = 48
@@ -215,6 +216,9 @@ def _bind(lib):
         "bcnf_add_layernorm_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _vp, _vp, _vp, _vp]),
         "bcnf_add_layernorm_work_bytes": (_i32, [_i64, _i32, _pi64]),
         "bcnf_add_layernorm_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+        "bcnf_lstm_forward": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp,
+                                     _vp]),
+        "bcnf_lstm_backward": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
         "bcnf_status_string": (ctypes.c_char_p, [_i32]),
         "bcnf_abi_version": (_i32, []),
     }

@@ -25,9 +25,9 @@ import torch
 import torch.nn as nn
 
 from bcnf_amd.factories import FeatureNetworkFactory, LayerFactory
-from bcnf_amd.feature_network import (ConcatenateCondition, DualDomainTransformer, FeatureNetwork, FeatureNetworkStack,
-                                      FullyConnectedFeatureNetwork, HIPLinear, LSTMFeatureNetwork, Transformer,
-                                      bind_rng_owner)
+from bcnf_amd.feature_network import (ConcatenateCondition, DualDomainLSTM, DualDomainTransformer, FeatureNetwork,
+                                      FeatureNetworkStack, FullyConnectedFeatureNetwork, HIPLinear,
+                                      LSTMFeatureNetwork, Transformer, bind_rng_owner)
 from bcnf_amd.fft_stack import FFTWideStack
 from bcnf_amd.fused import (FusedStack, StackBase, StackConfig, stack_forward, stack_hybrid, stack_inverse, stack_nll,
                             stack_nll_fold)
@@ -612,7 +612,7 @@ class CondRealNVP_v2(ConditionalInvertibleLayer):
 
     # The wide family's training path: the feature network's LAST Linear (FC_large: 310 -> 1360; LSTM_large with
     # pool_dim=1 and mean pooling: 280 -> 1360, mean over time commutes with it; a Transformer's `output`; the last
-    # Linear of a DualDomainTransformer's `fc`) folds into the condition projection
+    # Linear of a DualDomainTransformer's or DualDomainLSTM's `fc`) folds into the condition projection
     # (bcnf_amd/wide.py, bcnf_wide_fold_*): the layers before it run as usual and hand x to the stack.
     def _wide_fold(self, y, conditions):
         if not self.fold_features or type(self._fused) is not WideStack or len(conditions) != 1 or y.requires_grad:
@@ -636,7 +636,7 @@ class CondRealNVP_v2(ConditionalInvertibleLayer):
         elif isinstance(fn, Transformer):
             x = fn.first_token(c)                              # the dropped-out first token; `output` folds
             lin = fn.output
-        elif isinstance(fn, DualDomainTransformer):
+        elif isinstance(fn, (DualDomainTransformer, DualDomainLSTM)):
             mods = list(fn.fc.nn)
             if not mods or type(mods[-1]) not in (nn.Linear, HIPLinear):
                 return None

@@ -14,6 +14,10 @@ Restated from the reference's behaviour (src/bcnf/models/feature_network.py); th
   layers run on the MFMA GEMMs over (B S, d) rows and the attention core and each residual + LayerNorm as one HIP
   launch per direction (bcnf_amd/csrc/bcnf_attn.hip); CPU tensors and shapes outside the kernels' limits run the
   reference's chain of torch ops. A head split that does not divide (trf_size % n_heads != 0) raises on forward.
+* VerboseLSTM / DualDomainLSTM  feature_network.py:310-398 -- same kwargs, submodule names and state_dict keys (single-
+  layer nn.LSTM modules in a ModuleList); on fp32 GPU tensors with hidden % 16 == 0, 16 <= hidden <= 128 each layer
+  runs its input projection on the MFMA GEMMs and the recurrence of both directions as one HIP launch
+  (bcnf_amd/csrc/bcnf_lstm.hip); CPU tensors and other shapes run the nn.LSTM modules.
 """
 from __future__ import annotations
 
@@ -498,6 +502,183 @@ class DualDomainTransformer(FeatureNetwork):
         return self.fc(self.combined(x))
 
 
+LSTM_MIN_HIDDEN = 16       # bcnf_lstm_*: hidden % 16 == 0, 16 <= hidden <= 128 (include/bcnf_amd.h)
+LSTM_MAX_HIDDEN = 128
+
+
+def _linear_work(N, rows: int, k: int, n: int, device) -> torch.Tensor:
+    wb = N.call_raw("bcnf_linear_work_bytes", rows, k, n)
+    return torch.empty(max(wb // 4, 1), dtype=torch.float32, device=device)
+
+
+class _LSTMLayerFn(torch.autograd.Function):
+    """One single-layer nn.LSTM (batch_first, zero initial state) on its own parameter tensors: per direction the input
+    projection P = x W_ih^T + b_ih over all (B S) rows as one GEMM (bcnf_linear_forward), then the recurrence of both
+    directions in ONE launch (bcnf_lstm_forward), which writes direction d at columns d H .. of the (B, S, dirs H)
+    output -- no cat, no per-step kernels. Backward: one bcnf_lstm_backward for dP, then bcnf_linear_backward for
+    (dx, dW_ih, db_ih) on x and for dW_hh on h_prev, the output shifted one step against the direction;
+    db_hh = db_ih."""
+
+    @staticmethod
+    def forward(ctx, x, hidden, *params):
+        from bcnf_amd import _native as N
+        dirs = len(params) // 4
+        batch, seq, k = x.shape
+        rows = batch * seq
+        x2 = x.reshape(rows, k)
+        st = N.stream_handle(x.device)
+        opts = dict(dtype=torch.float32, device=x.device)
+        proj = torch.empty((dirs, rows, 4 * hidden), **opts)
+        for d in range(dirs):
+            w_ih, _, b_ih, _ = params[4 * d:4 * d + 4]
+            N.call("bcnf_linear_forward", x2, w_ih, b_ih, rows, k, 4 * hidden, proj[d], st)
+        out = torch.empty((batch, seq, dirs * hidden), **opts)
+        save = any(ctx.needs_input_grad)     # all False under no_grad: nothing is saved at inference
+        gates = torch.empty((dirs, rows, 4 * hidden), **opts) if save else None
+        cells = torch.empty((dirs, rows, hidden), **opts) if save else None
+        rev = 4 if dirs == 2 else 0
+        N.call("bcnf_lstm_forward", proj[0], proj[1] if dirs == 2 else None, 4 * hidden, params[1],
+               params[rev + 1] if dirs == 2 else None, params[3], params[rev + 3] if dirs == 2 else None, batch, seq,
+               hidden, dirs, out, dirs * hidden, gates, cells, st)
+        if save:
+            ctx.save_for_backward(x2, out, gates, cells, *params)
+        ctx.dims = (batch, seq, k, hidden, dirs)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from bcnf_amd import _native as N
+        x2, out, gates, cells, *params = ctx.saved_tensors
+        batch, seq, k, hidden, dirs = ctx.dims
+        rows = batch * seq
+        st = N.stream_handle(x2.device)
+        dout = dout.contiguous()
+        dproj = torch.empty((dirs, rows, 4 * hidden), dtype=torch.float32, device=x2.device)
+        N.call("bcnf_lstm_backward", dout, dirs * hidden, gates, cells, params[1], params[5] if dirs == 2 else None,
+               batch, seq, hidden, dirs, dproj[0], dproj[1] if dirs == 2 else None, 4 * hidden, st)
+        need = ctx.needs_input_grad
+        dx = None
+        grads = []
+        for d in range(dirs):
+            w_ih, w_hh, b_ih, b_hh = params[4 * d:4 * d + 4]
+            n_ih, n_hh, n_bi, n_bh = need[2 + 4 * d:6 + 4 * d]
+            dxd = torch.empty_like(x2) if need[0] else None
+            need_b = (n_bi and b_ih is not None) or (n_bh and b_hh is not None)
+            dw_ih = torch.empty_like(w_ih) if (n_ih or need_b) else None
+            db = torch.empty(4 * hidden, dtype=torch.float32, device=x2.device) if need_b else None
+            if dxd is not None or dw_ih is not None:
+                work = _linear_work(N, rows, k, 4 * hidden, x2.device) if dw_ih is not None else None
+                N.call("bcnf_linear_backward", x2, w_ih, dproj[d], rows, k, 4 * hidden, dxd, dw_ih, db, work, st)
+            dw_hh = None
+            if n_hh:
+                # h_prev: h of the forward's previous step, zeros at its first
+                hp = torch.zeros((batch, seq, hidden), dtype=torch.float32, device=x2.device)
+                if seq > 1:
+                    h = out[:, :, d * hidden:(d + 1) * hidden]
+                    if d == 0:
+                        hp[:, 1:].copy_(h[:, :-1])
+                    else:
+                        hp[:, :-1].copy_(h[:, 1:])
+                dw_hh = torch.empty_like(w_hh)
+                N.call("bcnf_linear_backward", hp, w_hh, dproj[d], rows, hidden, 4 * hidden, None, dw_hh, None,
+                       _linear_work(N, rows, hidden, 4 * hidden, x2.device), st)
+            if dxd is not None:
+                dx = dxd if dx is None else dx.add_(dxd)
+            grads += [dw_ih if n_ih else None, dw_hh, db if (n_bi and b_ih is not None) else None,
+                      db.clone() if (n_bh and b_hh is not None) else None]
+        return (dx.view(batch, seq, k) if dx is not None else None), None, *grads
+
+
+class VerboseLSTM(nn.Module):
+    """feature_network.py:310-347: `lstm`, a ModuleList of single-layer batch_first nn.LSTM modules with an nn.Dropout
+    between them when dropout > 0 (same state_dict keys, the Dropout entries' index gaps included). fp32 GPU tensors
+    with hidden % 16 == 0 and 16 <= hidden <= 128 run each layer as projection GEMM(s) + one recurrence launch on the
+    nn.LSTM's own parameters (_LSTMLayerFn; its backward works in eval mode); everything else, and `fused = False`,
+    runs the nn.LSTM modules themselves."""
+
+    fused = True        # False: the nn.LSTM modules (fallback tests, tools/dlstm_feature_ab.py)
+
+    def __init__(self, input_size: int, hidden_size: int, num_layers: int, dropout: float = 0.0,
+                 bidirectional: bool = False) -> None:
+        super().__init__()
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        self.num_layers = num_layers
+        self.dropout = dropout
+        self.bidirectional = bidirectional
+        self.lstm = nn.ModuleList()
+        for _ in range(num_layers - 1):
+            self.lstm.append(nn.LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=1,
+                                     bidirectional=bidirectional, batch_first=True))
+            input_size = hidden_size * (2 if bidirectional else 1)
+            if dropout > 0:
+                self.lstm.append(nn.Dropout(p=dropout))
+        self.lstm.append(nn.LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=1,
+                                 bidirectional=bidirectional, batch_first=True))
+
+    def _layer(self, layer: nn.LSTM, x: torch.Tensor) -> torch.Tensor:
+        hidden = layer.hidden_size
+        names = [n for names in layer._all_weights for n in names]
+        params = [getattr(layer, n) for n in names]
+        if (self.fused and x.dim() == 3 and x.numel() > 0 and layer.bias and layer.proj_size == 0
+                and hidden % 16 == 0 and LSTM_MIN_HIDDEN <= hidden <= LSTM_MAX_HIDDEN and _on_kernels(x, *params)
+                and all(p.is_cuda for p in params)):
+            return _LSTMLayerFn.apply(x.contiguous(), hidden, *params)
+        return layer(x)[0]
+
+    def forward(self, x: torch.Tensor, return_h: bool = True):
+        """(x, h): the last layer's output (B, S, dirs H) and every layer's, (B, num_layers, S, dirs H), as the
+        reference; return_h=False skips filling h and returns (x, None)."""
+        h = torch.empty(self.num_layers, x.size(0), x.size(1), self.hidden_size * (2 if self.bidirectional else 1),
+                        device=x.device) if return_h else None
+        lstm_index = 0
+        for layer in self.lstm:
+            if isinstance(layer, nn.LSTM):
+                x = self._layer(layer, x)
+                if return_h:
+                    h[lstm_index] = x
+                lstm_index += 1
+            else:
+                x = layer(x)
+        return x, (h.permute(1, 0, 2, 3) if return_h else None)
+
+
+class DualDomainLSTM(FeatureNetwork):
+    """feature_network.py:350-398: a VerboseLSTM on x, one on cat(rfft(x, dim=1).real, .imag) (S // 2 + 1 bins of
+    2 input_size values), both pooled over dim 1 (mean or max), and a FullyConnectedFeatureNetwork on the concatenated
+    (B, 2 H dirs) result."""
+
+    def __init__(self, input_size: int, hidden_size: int, fc_sizes: list[int], fc_dropout: float = 0.0,
+                 num_layers: int = 1, dropout: float = 0.0, bidirectional: bool = False, pooling: str = "mean") -> None:
+        super().__init__()
+        if pooling not in ("mean", "max"):
+            raise ValueError(f"Invalid pooling method: {pooling}")
+        self.input_size = input_size
+        self.output_size = fc_sizes[-1]
+        self.pooling = pooling
+        self.lstm = VerboseLSTM(input_size, hidden_size, num_layers, dropout, bidirectional)
+        self.frequency_lstm = VerboseLSTM(input_size * 2, hidden_size, num_layers, dropout, bidirectional)
+        self.fc_sizes = [hidden_size * (2 if bidirectional else 1) * 2] + list(fc_sizes)
+        self.fc = FullyConnectedFeatureNetwork(sizes=self.fc_sizes, dropout=fc_dropout)
+
+    def _pool(self, x: torch.Tensor) -> torch.Tensor:
+        if self.pooling == "mean":
+            return x.mean(dim=1)
+        if self.pooling == "max":
+            return x.max(dim=1).values
+        raise ValueError(f"Invalid pooling method: {self.pooling}")
+
+    def combined(self, x: torch.Tensor) -> torch.Tensor:
+        """The input of `fc`: (B, 2 H dirs) = [pooled time branch | pooled frequency branch]."""
+        x_lstm, _ = self.lstm(x, return_h=False)
+        freq = torch.fft.rfft(x, dim=1)
+        x_freq, _ = self.frequency_lstm(torch.cat([freq.real, freq.imag], dim=-1), return_h=False)
+        return torch.cat([self._pool(x_lstm), self._pool(x_freq)], dim=1)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fc(self.combined(x))
+
+
 class FeatureNetworkStack(FeatureNetwork):
     def __init__(self, feature_networks: list[nn.Module | None] | None = None) -> None:
         super().__init__()
@@ -528,5 +709,6 @@ FEATURE_NETWORKS: dict[str, Any] = {
     "LSTM": LSTMFeatureNetwork,
     "Transformer": Transformer,
     "DualDomainTransformer": DualDomainTransformer,
+    "DualDomainLSTM": DualDomainLSTM,
     "ConcatenateCondition": ConcatenateCondition,
 }

@@ -516,6 +516,34 @@ int bcnf_add_layernorm_backward(const float* x, const float* r, const float* gam
                                 const float* rstd, const float* dy, int64_t rows, int32_t d, float* dx, float* dgamma,
                                 float* dbeta, void* work, void* stream);
 
+/* ---- LSTM layer (feature_network.py:310-398: VerboseLSTM's single-layer nn.LSTM modules under DualDomainLSTM) ------
+ * The serial part of ONE layer, both directions in one launch; gate order and formulas are torch's (i, f, g, o):
+ *   gates_t = P_t + h_{t-1} W_hh^T + b_hh,  c_t = s(f) c_{t-1} + s(i) tanh(g),  h_t = s(o) tanh(c_t),  h_0 = c_0 = 0,
+ * the reverse direction walking t = S - 1 .. 0. The input projection P = x W_ih^T + b_ih is NOT part of it (one
+ * bcnf_linear_forward per direction over all B * S rows), nor are the weight gradients: dW_ih, db_ih and dx come from
+ * bcnf_linear_backward on the backward's dP, dW_hh (and db_hh = db_ih) from the same call with x := h_prev, the output
+ * sequence shifted one step against the direction with zeros at its first step. fp32, stream-ordered, stateless, no
+ * atomics; every sum runs in a fixed order (same inputs, same bits).
+ *
+ * Limits: hidden % 16 == 0, 16 <= hidden <= 128, seq_len >= 1, batch >= 1, dirs 1 or 2, ldp >= 4 * hidden,
+ * ldo >= dirs * hidden; anything else returns BCNF_ERR_ARG and launches nothing. The *_rev pointers are read only
+ * when dirs == 2; b_hh_* may be NULL (no bias).
+ *
+ * Layouts. p_fwd / p_rev (and dp_fwd / dp_rev): (B * S) rows, row b * S + t, `ldp` floats apart, 4 * hidden floats
+ * each, gate g at columns g * hidden ... w_hh_*: (4 * hidden, hidden) row-major. out (and dout): (B * S) rows `ldo`
+ * floats apart, direction d at columns d * hidden .. (d + 1) * hidden - 1 (no concatenation; columns past
+ * dirs * hidden of a row are neither read nor written). gates (dirs, B * S, 4 * hidden) and cells (dirs, B * S,
+ * hidden), contiguous: the activated gates and c_t the backward reads; both NULL (inference: nothing saved) or both
+ * given. tanh(c_t) is recomputed. backward: dp_* receive the gradient of the pre-activation gates, step by step
+ * against the forward's order (dh = dout_t + dh_rec, the gate derivatives, dP_t, dh_rec = dP_t W_hh). */
+int bcnf_lstm_forward(const float* p_fwd, const float* p_rev, int64_t ldp, const float* w_hh_fwd,
+                      const float* w_hh_rev, const float* b_hh_fwd, const float* b_hh_rev, int64_t batch,
+                      int32_t seq_len, int32_t hidden, int32_t dirs, float* out, int64_t ldo, float* gates,
+                      float* cells, void* stream);
+int bcnf_lstm_backward(const float* dout, int64_t ldo, const float* gates, const float* cells, const float* w_hh_fwd,
+                       const float* w_hh_rev, int64_t batch, int32_t seq_len, int32_t hidden, int32_t dirs,
+                       float* dp_fwd, float* dp_rev, int64_t ldp, void* stream);
+
 /* ---- Calibration (eval/calibration.py:20-48, compute_y_hat_ranks) -----------------------------------------------
  * counts[i * dim + d] += #{ s < n_draws : y_hat[(s * n_rows + i) * dim + d] < y[i * dim + d] } for the (n_draws, n_rows,
  * dim) draws of sample(outer=True); counts is uint32 and accumulates, so draws can be fed in chunks. */
