@@ -5,6 +5,7 @@ forward / inverse / sample API and state_dict layout, with the coupling stack on
 """
 from bcnf_amd.cnf import (ActNorm, CondRealNVP_v2, ConditionalAffineCouplingLayer, ConditionalInvertibleLayer,
                           ConditionalNestedNeuralNetwork, InvertibleLayer, OrthonormalTransformation)
+from bcnf_amd.cnn import CNN
 from bcnf_amd.feature_network import (ConcatenateCondition, DualDomainLSTM, DualDomainTransformer, FeatureNetwork,
                                       FeatureNetworkStack, FullyConnectedFeatureNetwork, LSTMFeatureNetwork,
                                       Transformer, VerboseLSTM)
@@ -15,7 +16,7 @@ __all__ = [
     "ActNorm", "CondRealNVP_v2", "ConditionalAffineCouplingLayer", "ConditionalInvertibleLayer",
     "ConditionalNestedNeuralNetwork", "InvertibleLayer", "OrthonormalTransformation", "ConcatenateCondition",
     "FeatureNetwork", "FeatureNetworkStack", "FullyConnectedFeatureNetwork", "LSTMFeatureNetwork",
-    "Transformer", "DualDomainTransformer", "VerboseLSTM", "DualDomainLSTM",
+    "Transformer", "DualDomainTransformer", "VerboseLSTM", "DualDomainLSTM", "CNN",
     "ParameterIndexMapping", "inn_nll_loss", "load_config", "log_prob_from_latent",
     "posterior_mode",
 ]

@@ -47,6 +47,7 @@ EXPORTS = (
     "bcnf_attn_forward", "bcnf_attn_backward", "bcnf_add_layernorm_forward", "bcnf_add_layernorm_work_bytes",
     "bcnf_add_layernorm_backward",
     "bcnf_lstm_forward", "bcnf_lstm_backward",
+    "bcnf_conv_block_forward", "bcnf_conv_block_work_bytes", "bcnf_conv_block_backward",
 )
 ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
 MAX_TENSORS = 48
@@ -219,6 +220,11 @@ def _bind(lib):
         "bcnf_lstm_forward": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp,
                                      _vp]),
         "bcnf_lstm_backward": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+        "bcnf_conv_block_forward": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                           ctypes.c_float, _vp, _i32, _vp, _vp, _vp]),
+        "bcnf_conv_block_work_bytes": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_float, _pi64]),
+        "bcnf_conv_block_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                            ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
         "bcnf_status_string": (ctypes.c_char_p, [_i32]),
         "bcnf_abi_version": (_i32, []),
     }

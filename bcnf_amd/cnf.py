@@ -24,6 +24,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from bcnf_amd.cnn import CNN
 from bcnf_amd.factories import FeatureNetworkFactory, LayerFactory
 from bcnf_amd.feature_network import (ConcatenateCondition, DualDomainLSTM, DualDomainTransformer, FeatureNetwork,
                                       FeatureNetworkStack, FullyConnectedFeatureNetwork, HIPLinear,
@@ -350,7 +351,7 @@ class CondRealNVP_v2(ConditionalInvertibleLayer):
         fns = getattr(self, "feature_network_stack", None)
         if self.n_conditions > 0 and fns is not None:
             for fn in fns.feature_networks:
-                if isinstance(fn, FullyConnectedFeatureNetwork):
+                if isinstance(fn, (FullyConnectedFeatureNetwork, CNN)):
                     bind_rng_owner(fn, self)
 
     # copy.deepcopy / pickle: the fused stack (ctypes descriptor, flat buffers whose views ARE the parameters, a grad

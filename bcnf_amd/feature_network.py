@@ -18,6 +18,8 @@ Restated from the reference's behaviour (src/bcnf/models/feature_network.py); th
   layer nn.LSTM modules in a ModuleList); on fp32 GPU tensors with hidden % 16 == 0, 16 <= hidden <= 128 each layer
   runs its input projection on the MFMA GEMMs and the recurrence of both directions as one HIP launch
   (bcnf_amd/csrc/bcnf_lstm.hip); CPU tensors and other shapes run the nn.LSTM modules.
+* CNN  models/cnn.py -- in bcnf_amd/cnn.py (it registers itself in FEATURE_NETWORKS below); FeatureRngMixin here is the
+  dropout Philox state it shares with FullyConnectedFeatureNetwork.
 """
 from __future__ import annotations
 
@@ -144,28 +146,9 @@ class ConcatenateCondition(FeatureNetwork):
         return x
 
 
-class FullyConnectedFeatureNetwork(FeatureNetwork):
-    def __init__(self, sizes: list[int], activation: Type[nn.Module] = nn.GELU, dropout: float = 0.0,
-                 batch_norm: bool = False) -> None:
-        super().__init__()
-        self.input_size = sizes[0]
-        self.output_size = sizes[-1]
-        self.output_size_lin = sizes[-1]
-        self.nn = nn.Sequential()
-        if len(sizes) < 2:
-            self.nn.append(nn.Identity())
-            return
-        for a, b in zip(sizes[:-2], sizes[1:-1]):
-            self.nn.append(HIPLinear(a, b))
-            if batch_norm:
-                self.nn.append(nn.BatchNorm1d(b))
-            self.nn.append(activation())
-            if dropout > 0.0:
-                self.nn.append(nn.Dropout(dropout))
-        self.nn.append(HIPLinear(sizes[-2], sizes[-1]))
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.run(x.view(x.size(0), -1))
+class FeatureRngMixin:
+    """The device Philox (seed, offset) state a feature network's fused dropout draws from (FullyConnected's
+    Linear + GELU + Dropout layers, the CNN's convolution blocks)."""
 
     # Philox stream of the fused dropout: the owning CondRealNVP_v2's coupling (seed, offset) state when one is bound
     # (bind_rng_owner; a registry outside the module, so deepcopy / pickle of this module never carry a reference to
@@ -174,7 +157,7 @@ class FullyConnectedFeatureNetwork(FeatureNetwork):
     # Advancing: the owner's coupling launch bumps the shared offset once per training step when the coupling itself
     # drops out (and a feature draw that no coupling launch followed -- this network run on its own -- is advanced
     # at the next draw, StackBase.feature_rng_state); otherwise (coupling dropout 0, the owner in eval mode or
-    # elsewhere, no owner) run() bumps it after the network's last fused dropout layer -- a device-side add,
+    # elsewhere, no owner) the network bumps it after its last fused dropout layer -- a device-side add,
     # replay-safe in HIP graphs -- so every training step draws fresh feature masks.
     _own_rng = None
 
@@ -199,6 +182,30 @@ class FullyConnectedFeatureNetwork(FeatureNetwork):
             seed = (torch.cuda.initial_seed() * 0x9E3779B97F4A7C15 + 0xFEA7) & ((1 << 62) - 1)
             self._own_rng = torch.tensor([seed, 0], dtype=torch.int64, device=device)
         return self._own_rng, False
+
+
+class FullyConnectedFeatureNetwork(FeatureRngMixin, FeatureNetwork):
+    def __init__(self, sizes: list[int], activation: Type[nn.Module] = nn.GELU, dropout: float = 0.0,
+                 batch_norm: bool = False) -> None:
+        super().__init__()
+        self.input_size = sizes[0]
+        self.output_size = sizes[-1]
+        self.output_size_lin = sizes[-1]
+        self.nn = nn.Sequential()
+        if len(sizes) < 2:
+            self.nn.append(nn.Identity())
+            return
+        for a, b in zip(sizes[:-2], sizes[1:-1]):
+            self.nn.append(HIPLinear(a, b))
+            if batch_norm:
+                self.nn.append(nn.BatchNorm1d(b))
+            self.nn.append(activation())
+            if dropout > 0.0:
+                self.nn.append(nn.Dropout(dropout))
+        self.nn.append(HIPLinear(sizes[-2], sizes[-1]))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.run(x.view(x.size(0), -1))
 
     def run(self, x: torch.Tensor, upto: int | None = None) -> torch.Tensor:
         """Modules [0, upto) of the MLP on the flattened input. Each Linear -> GELU(exact) [-> Dropout] group of fp32

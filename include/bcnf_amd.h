@@ -544,6 +544,46 @@ int bcnf_lstm_backward(const float* dout, int64_t ldo, const float* gates, const
                        const float* w_hh_rev, int64_t batch, int32_t seq_len, int32_t hidden, int32_t dirs,
                        float* dp_fwd, float* dp_rev, int64_t ldp, void* stream);
 
+/* ---- CNN layer (models/cnn.py: Conv2d -> ReLU -> Dropout -> MaxPool2d(2, 2), the unit the CNN feature network
+ * repeats) --------------------------------------------------------------------------------------------------------
+ * ONE layer per launch and direction; nothing at the convolution's resolution is written:
+ *   pre = conv2d(x, weight, bias), stride 1, zero padding (pad_h, pad_w): (n_images, c_out, Hc, Wc) with
+ *         Hc = height + 2 pad_h - ksize + 1, Wc = width + 2 pad_w - ksize + 1,
+ *   a   = relu(pre) * keep / (1 - p),
+ *   y   = the 2 x 2 / stride-2 maximum of a, floor mode: (n_images, c_out, Hc / 2, Wc / 2); an odd last row or column
+ *         of pre belongs to no window (and receives no gradient).
+ * fp32, NCHW contiguous: x (n_images, c_in, height, width), weight (c_out, c_in, ksize, ksize), bias (c_out,
+ * nullable). Stream-ordered, stateless, no atomics; every sum runs in a fixed order (same inputs, same bits).
+ *
+ * Limits: 1 <= ksize <= 8, 1 <= c_in, c_out <= 32, 0 <= pad_h, pad_w <= ksize - 1, Hc >= 2 and Wc >= 2,
+ * n_images >= 1, 0 <= p < 1; anything else returns BCNF_ERR_ARG and launches nothing.
+ *
+ * code (uint8, the shape of y; NULL = inference, nothing saved): bits 0-1 = the winner's position in its window,
+ * 0 .. 3 in row-major order (the first of equal values wins, as torch's max_pool2d), bit 2 = the winner is positive --
+ * the only case in which a gradient flows (ReLU active and the unit kept).
+ *
+ * Dropout (p > 0 and rng_state != NULL, else none): rng_state is the device (seed, offset) pair of the library's
+ * other dropout layers. Element e -- the flat index of a unit in (n_images, c_out, Hc, Wc) -- keeps iff
+ * u32(e) >= thresh32(p) = round(p 2^32), where u32(e) is word e & 3 of Philox4x32-10 with
+ *   counter (e >> 2 low half, e >> 2 high half, offset low half, offset high half),
+ *   key     (seed low half ^ salt * 0x9E3779B9, seed high half ^ 0x40000000)
+ * -- the feature Linear layers' key has 0x80000000 there, so the same (seed, offset, salt) gives both kinds of layer
+ * independent draws. The backward needs no RNG: a dropped unit is a zero, which never wins with bit 2 set.
+ *
+ * backward: g = dy * [bit 2] / (1 - p) at each window's winner, zero elsewhere; dx (the shape of x, nullable: the
+ * first layer's input is the images) = the transposed convolution of g, dweight / dbias (nullable) are summed per
+ * (workgroup, row slice) into `work` (caller-owned, 16-byte aligned, bcnf_conv_block_work_bytes(...) bytes; may be NULL
+ * when neither is wanted) and reduced in index order by a second launch. */
+int bcnf_conv_block_forward(const float* x, const float* weight, const float* bias, int64_t n_images, int32_t c_in,
+                            int32_t height, int32_t width, int32_t c_out, int32_t ksize, int32_t pad_h, int32_t pad_w,
+                            float p, const uint64_t* rng_state, int32_t salt, float* y, uint8_t* code, void* stream);
+int bcnf_conv_block_work_bytes(int64_t n_images, int32_t c_in, int32_t height, int32_t width, int32_t c_out,
+                               int32_t ksize, int32_t pad_h, int32_t pad_w, float p, int64_t* bytes);
+int bcnf_conv_block_backward(const float* x, const float* weight, const float* dy, const uint8_t* code,
+                             int64_t n_images, int32_t c_in, int32_t height, int32_t width, int32_t c_out,
+                             int32_t ksize, int32_t pad_h, int32_t pad_w, float p, float* dx, float* dweight,
+                             float* dbias, void* work, void* stream);
+
 /* ---- Calibration (eval/calibration.py:20-48, compute_y_hat_ranks) -----------------------------------------------
  * counts[i * dim + d] += #{ s < n_draws : y_hat[(s * n_rows + i) * dim + d] < y[i * dim + d] } for the (n_draws, n_rows,
  * dim) draws of sample(outer=True); counts is uint32 and accumulates, so draws can be fed in chunks. */
