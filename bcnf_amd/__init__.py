@@ -9,6 +9,9 @@ from bcnf_amd.cnn import CNN
 from bcnf_amd.feature_network import (ConcatenateCondition, DualDomainLSTM, DualDomainTransformer, FeatureNetwork,
                                       FeatureNetworkStack, FullyConnectedFeatureNetwork, LSTMFeatureNetwork,
                                       Transformer, VerboseLSTM)
+from bcnf_amd.data import VideoBatches
+from bcnf_amd.render import (camera, camera_basis, get_cams_position, record_trajectory, render_device, render_host,
+                             standard_normals, visibility)
 from bcnf_amd.sampling import posterior_mode
 from bcnf_amd.utils import ParameterIndexMapping, inn_nll_loss, load_config, log_prob_from_latent
 
@@ -18,5 +21,6 @@ __all__ = [
     "FeatureNetwork", "FeatureNetworkStack", "FullyConnectedFeatureNetwork", "LSTMFeatureNetwork",
     "Transformer", "DualDomainTransformer", "VerboseLSTM", "DualDomainLSTM", "CNN",
     "ParameterIndexMapping", "inn_nll_loss", "load_config", "log_prob_from_latent",
-    "posterior_mode",
+    "posterior_mode", "camera", "record_trajectory", "camera_basis", "get_cams_position", "render_device",
+    "render_host", "standard_normals", "visibility", "VideoBatches",
 ]

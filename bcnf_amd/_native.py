@@ -48,6 +48,7 @@ EXPORTS = (
     "bcnf_add_layernorm_backward",
     "bcnf_lstm_forward", "bcnf_lstm_backward",
     "bcnf_conv_block_forward", "bcnf_conv_block_work_bytes", "bcnf_conv_block_backward",
+    "bcnf_render_frames",
 )
 ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
 MAX_TENSORS = 48
@@ -225,6 +226,8 @@ def _bind(lib):
         "bcnf_conv_block_work_bytes": (_i32, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_float, _pi64]),
         "bcnf_conv_block_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                             ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
+        "bcnf_render_frames": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, ctypes.c_uint64,
+                                      ctypes.c_uint64, _i64, _vp, _i32, _vp, _vp, _vp]),
         "bcnf_status_string": (ctypes.c_char_p, [_i32]),
         "bcnf_abi_version": (_i32, []),
     }

@@ -106,3 +106,84 @@ class DeviceBatches:
         idx = self._perm[self._pos:self._pos + self.batch]
         self._pos += self.batch
         return idx
+
+
+def sample_cameras(n: int, seed: int = 2024_03_25):
+    """The camera parameters of n two-camera samples from the priors of configs/data/config.yaml, as generate_data
+    arranges them (sampling.py:245-254, 363): cam_radian (n, 2) = [cam1 at 0, U(0, 2 pi)], cam_radius (n,) ~ Gamma(2.5,
+    5), cam_angles (n, 2) ~ Gamma(3, 10) degrees, cam_heights (n, 2) ~ U(0.4, 1.4). float64."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    cam_radian = np.stack([np.zeros(n), rng.uniform(0.0, 6.283185307, n)], 1)
+    cam_radius = rng.gamma(2.5, 5.0, n)
+    cam_angles = rng.gamma(3.0, 10.0, (n, 2))
+    cam_heights = rng.uniform(0.4, 1.4, (n, 2))
+    return cam_radian, cam_radius, cam_angles, cam_heights
+
+
+class VideoBatches:
+    """A pool of simulated samples served as (y, videos, cam_tail) batches for the videos_* configs: physics parameters
+    and trajectories from simulate() (T = 2.0, dt = 0.067: 30 frames), camera parameters from sample_cameras(), the two
+    cameras placed by get_cams_position (the reference's, bug for bug) and every frame rendered on the device by
+    bcnf_amd.render.render_device.
+
+    videos (batch, 2, 30, 90, 160) float32; cam_tail (batch, 7) float32 = cam_radian (2), cam_radius (1), cam_angles
+    (2), cam_heights (2), the order the configs' second condition concatenates them. The pool is rendered once; with
+    online=True only the parameters are kept and each batch is rendered when it is served, with `offset` advanced by
+    one per batch, so every batch sees fresh camera noise."""
+
+    T, DT, N_CAMS = 2.0, 0.067, 2
+
+    def __init__(self, n_pool: int, batch: int, device, seed: int = 2024_03_25, normalize: bool = True,
+                 online: bool = False, n_samples: int = 5000, fov_horizontal: float = 70.0):
+        import torch
+        from .render import get_cams_position
+        y, traj = simulate(n_pool, seed, T=self.T, dt=self.DT)
+        cam_radian, cam_radius, cam_angles, cam_heights = sample_cameras(n_pool, seed + 1)
+        self.radius = y[:, PARAMETERS.index('r')].astype(np.float64)
+        self.cam_pos = get_cams_position(cam_radian, cam_radius, cam_heights)          # (n, 2, 3)
+        self.cam_angles = cam_angles
+        tail = np.concatenate([cam_radian, cam_radius[:, None], cam_angles, cam_heights], 1).astype(np.float32)
+        y_t = torch.from_numpy(y)
+        if normalize:
+            y_t = (y_t - y_t.mean(0)) / (y_t.std(0) + 1e-6)
+        self.device = torch.device(device)
+        self.y = y_t.to(self.device)
+        self.traj = torch.from_numpy(traj).to(self.device, torch.float64)
+        self.cam_tail = torch.from_numpy(tail).to(self.device)
+        self.batch, self.n, self.seed, self.online = batch, n_pool, seed, online
+        self.n_samples, self.fov_horizontal = n_samples, fov_horizontal
+        self.offset = 0
+        self.gen = torch.Generator(device="cpu").manual_seed(seed)
+        self._perm = None
+        self._pos = 0
+        self.videos = None if online else self.render(np.arange(n_pool))
+
+    def render(self, rows):
+        """float32 videos (len(rows), 2, 30, 90, 160) of pool samples `rows` at the current offset, in ONE launch: the
+        sample at position k of `rows` draws with frame indices k * 60 .. k * 60 + 59."""
+        import torch
+        from .render import render_device
+        rows = np.asarray(rows, dtype=np.int64)
+        return render_device(self.traj[torch.from_numpy(rows).to(self.device)],self.cam_pos[rows], self.cam_angles[rows], self.radius[rows],
+                             fov_horizontal=self.fov_horizontal, n_samples=self.n_samples, seed=self.seed,
+                             offset=self.offset, device=self.device)
+
+    def next_indices(self):
+        import torch
+        if self._perm is None or self._pos + self.batch > self.n:
+            self._perm = torch.randperm(self.n, generator=self.gen)
+            self._pos = 0
+        idx = self._perm[self._pos:self._pos + self.batch]
+        self._pos += self.batch
+        return idx
+
+    def next_batch(self):
+        """(y (batch, 19), videos (batch, 2, 30, 90, 160), cam_tail (batch, 7)) on the device."""
+        idx = self.next_indices()
+        idx_d = idx.to(self.device)
+        if self.online:
+            videos = self.render(idx.numpy())
+            self.offset += 1
+        else:
+            videos = self.videos[idx_d]
+        return self.y[idx_d], videos, self.cam_tail[idx_d]

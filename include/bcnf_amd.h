@@ -35,6 +35,8 @@
  *   bcnf_rank_count      <- the rank count of compute_y_hat_ranks (eval/calibration.py:42-46)
  *   bcnf_resimulate      <- resimulate's per-draw physics_ODE_simulation map (simulation/resimulation.py:12-18,
  *                           49-56 -> simulation/physics.py:53-160)
+ *   bcnf_render_frames   <- camera() per frame of record_trajectory, per camera of generate_data
+ *                           (simulation/camera.py:30-150, simulation/sampling.py:366-368)
  */
 #ifndef BCNF_AMD_H
 #define BCNF_AMD_H
@@ -609,6 +611,40 @@ int bcnf_resimulate(const void* y_hat, int32_t y_hat_f64, int64_t n_draws, int64
                     const int32_t* param_cols, const double* fixed, const double* tgrid, int32_t steps, double dt,
                     int32_t break_on_impact, double rtol, double atol, int32_t max_attempts, double* x,
                     int32_t* attempts, int32_t* status, void* stream);
+
+/* ---- Camera (simulation/camera.py:74-150 camera(), looped by record_trajectory, camera.py:30-71, and over the two
+ * cameras of a sample by generate_data, sampling.py:366-368) -----------------------------------------------------------
+ * Renders n_frames frames of BCNF_RENDER_HEIGHT x BCNF_RENDER_WIDTH pixels in one launch, one workgroup per frame.
+ * Frame f: n_samples points ball_pos[f] + sigma[f] z_s (sigma = radius / 1.644854; z_s the three standard normals of
+ * sample s, below), seen from camera c = cam_index[f] (0 <= c < n_cams; anything else gives an all-zero frame with
+ * n_in[f] = -1): v = normalise(point - cam_pos[c]), ph = atan2(v . basis[c][1], v . basis[c][0]),
+ * th = atan2(v . basis[c][2], v . basis[c][0]) with basis[c] = (cam_dir, cam_orthogonal, cam_orthogonal_z) as rows, all
+ * in fp64. ph_edges (WIDTH + 1) and th_edges (HEIGHT + 1) are the np.linspace edge tables np.histogram2d builds; a sample
+ * counts in bin (i, j) iff ph_edges[i] <= ph < ph_edges[i + 1] and th_edges[j] <= th < th_edges[j + 1], the last edge
+ * of each table included, and is dropped outside the tables (or when an angle is NaN) -- the bins of
+ * np.searchsorted(edges, x, 'right') - 1, decided against the tables themselves. images[f][HEIGHT - 1 - j][i] =
+ * count / n_in[f] (the fp64 quotient rounded once to float, or kept as double with images_f64), n_in[f] = the samples
+ * of frame f that were counted; a frame with n_in[f] == 0 is all zeros = np.flipud(vals.T) of camera.py:139-150.
+ * counts (int32, the images' layout) and n_in (int32 per frame) are optional. images and counts 16-byte aligned; every
+ * pointer is device memory. Stream-ordered, stateless, LDS atomics only: same inputs, same bits.
+ *
+ * Draw rule (the reference draws from numpy's global stream, which no kernel can follow; bcnf_amd/render.py:
+ * standard_normals restates this rule in numpy and is its normative statement). Sample s of frame f draws
+ *   (w0, w1, w2, w3) = Philox4x32-10 with
+ *     counter (s, first_frame + f, offset low half, offset high half),
+ *     key     (seed low half, seed high half ^ 0xC0000000)   -- the dropout layers' keys carry 0x80000000 / 0x40000000
+ *                                                               or neither there, so one seed gives independent draws;
+ *   u_i = (w_i + 0.5) 2^-32, exact in fp64 and strictly inside (0, 1);
+ *   Box-Muller in fp64:  z_s = ( sqrt(-2 ln u0) cos(2 pi u1),  sqrt(-2 ln u0) sin(2 pi u1),  sqrt(-2 ln u2) cos(2 pi u3) ),
+ *   with 2 pi = 6.283185307179586.
+ * A frame's draws depend on (s, first_frame + f, offset, seed) only: not on n_frames, on the launch a frame is rendered
+ * in, or on n_samples (the first n of a longer draw are the draw of n). first_frame + n_frames <= 2^32. */
+#define BCNF_RENDER_WIDTH 160
+#define BCNF_RENDER_HEIGHT 90
+int bcnf_render_frames(const double* ball_pos, const int32_t* cam_index, const double* sigma, int64_t n_frames,
+                       const double* cam_pos, const double* basis, int32_t n_cams, const double* ph_edges,
+                       const double* th_edges, int32_t n_samples, uint64_t seed, uint64_t offset, int64_t first_frame,
+                       void* images, int32_t images_f64, int32_t* counts, int32_t* n_in, void* stream);
 
 
 const char* bcnf_status_string(int status);
