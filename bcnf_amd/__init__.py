@@ -10,6 +10,7 @@ from bcnf_amd.feature_network import (ConcatenateCondition, DualDomainLSTM, Dual
                                       FeatureNetworkStack, FullyConnectedFeatureNetwork, LSTMFeatureNetwork,
                                       Transformer, VerboseLSTM)
 from bcnf_amd.data import VideoBatches
+from bcnf_amd.generate import generate_data, generate_data_device, sample_candidates_host
 from bcnf_amd.render import (camera, camera_basis, get_cams_position, record_trajectory, render_device, render_host,
                              standard_normals, visibility)
 from bcnf_amd.sampling import posterior_mode
@@ -23,4 +24,5 @@ __all__ = [
     "ParameterIndexMapping", "inn_nll_loss", "load_config", "log_prob_from_latent",
     "posterior_mode", "camera", "record_trajectory", "camera_basis", "get_cams_position", "render_device",
     "render_host", "standard_normals", "visibility", "VideoBatches",
+    "generate_data", "generate_data_device", "sample_candidates_host",
 ]

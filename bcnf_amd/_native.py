@@ -48,7 +48,7 @@ EXPORTS = (
     "bcnf_add_layernorm_backward",
     "bcnf_lstm_forward", "bcnf_lstm_backward",
     "bcnf_conv_block_forward", "bcnf_conv_block_work_bytes", "bcnf_conv_block_backward",
-    "bcnf_render_frames",
+    "bcnf_render_frames", "bcnf_render_frames_at", "bcnf_render_lit", "bcnf_sample_candidates",
 )
 ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
 MAX_TENSORS = 48
@@ -228,6 +228,12 @@ def _bind(lib):
                                             ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
         "bcnf_render_frames": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, ctypes.c_uint64,
                                       ctypes.c_uint64, _i64, _vp, _i32, _vp, _vp, _vp]),
+        "bcnf_render_frames_at": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, ctypes.c_uint64,
+                                         ctypes.c_uint64, _vp, _vp, _i32, _vp, _vp, _vp]),
+        "bcnf_render_lit": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, ctypes.c_uint64,
+                                   ctypes.c_uint64, _i64, _vp, _vp, _vp]),
+        "bcnf_sample_candidates": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _i64, _i64, ctypes.c_double, _i32,
+                                          ctypes.c_double, ctypes.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
         "bcnf_status_string": (ctypes.c_char_p, [_i32]),
         "bcnf_abi_version": (_i32, []),
     }

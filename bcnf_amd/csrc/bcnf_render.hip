@@ -42,6 +42,7 @@ struct RenderArgs {
   const double* th_edges;    // [NTH + 1]
   int n_cams, n_samples;
   uint32_t key0, key1, off_lo, off_hi, first_frame;
+  const uint32_t* frame_index;     // [F] draw-rule frame indices, or NULL: first_frame + f
   void* images;              // [F][NTH][NPH] float or double
   int32_t* counts;           // [F][NTH][NPH], optional
   int32_t* n_in;             // [F], optional
@@ -73,13 +74,15 @@ struct Vec16<double> {
   static constexpr int N = 2;
 };
 
-template <typename TO>
+// IMAGES = false is the lit-frame pass (bcnf_render_lit): the same draws, geometry and range test, n_in only -- no
+// histogram, so no bins, no 57.6 KB of LDS and no image traffic.
+template <typename TO, bool IMAGES>
 __global__ __launch_bounds__(RENDER_WG, 4) void k_render(const RenderArgs a) {
-  __shared__ uint32_t hist[NPIX];                  // [th_bin][ph_bin]
+  __shared__ uint32_t hist[IMAGES ? NPIX : 4];     // [th_bin][ph_bin]
   __shared__ double s_ph[NPH + 1], s_th[NTH + 1];
   __shared__ uint32_t s_n;
   const int f = blockIdx.x, tid = threadIdx.x;
-  {
+  if constexpr (IMAGES) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     u32x4* h4 = reinterpret_cast<u32x4*>(hist);
     for (int e = tid; e < NPIX / 4; e += RENDER_WG) h4[e] = u32x4{0u, 0u, 0u, 0u};
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(RENDER_WG, 4) void k_render(const RenderArgs a) {
   __syncthreads();
   const double ph_lo = s_ph[0], ph_hi = s_ph[NPH], th_lo = s_th[0], th_hi = s_th[NTH];
   const double ph_iw = (double)NPH / (ph_hi - ph_lo), th_iw = (double)NTH / (th_hi - th_lo);
-  const uint32_t frame = a.first_frame + (uint32_t)f;
+  const uint32_t frame = a.frame_index ? a.frame_index[f] : a.first_frame + (uint32_t)f;
   uint32_t mine = 0;
   if (cam_ok) {
     for (int s = tid; s < a.n_samples; s += RENDER_WG) {
@@ -124,8 +127,10 @@ __global__ __launch_bounds__(RENDER_WG, 4) void k_render(const RenderArgs a) {
       const double d_th = v[0] * bs[6] + v[1] * bs[7] + v[2] * bs[8];
       const double ph = atan2(d_ph, d_dir), th = atan2(d_th, d_dir);
       if (ph >= ph_lo && ph <= ph_hi && th >= th_lo && th <= th_hi) {      // false for a NaN, as numpy drops it
-        const int bph = bin_of(s_ph, NPH, ph_iw, ph), bth = bin_of(s_th, NTH, th_iw, th);
-        atomicAdd(&hist[bth * NPH + bph], 1u);
+        if constexpr (IMAGES) {
+          const int bph = bin_of(s_ph, NPH, ph_iw, ph), bth = bin_of(s_th, NTH, th_iw, th);
+          atomicAdd(&hist[bth * NPH + bph], 1u);
+        }
         ++mine;
       }
     }
@@ -134,6 +139,7 @@ __global__ __launch_bounds__(RENDER_WG, 4) void k_render(const RenderArgs a) {
   __syncthreads();
   const uint32_t n = s_n;
   if (tid == 0 && a.n_in) a.n_in[f] = cam_ok ? (int32_t)n : -1;
+  if constexpr (!IMAGES) return;
   typedef typename Vec16<TO>::type vec_t;
   constexpr int VN = Vec16<TO>::N;
   vec_t* img = reinterpret_cast<vec_t*>(static_cast<TO*>(a.images) + (long long)f * NPIX);
@@ -169,15 +175,17 @@ __global__ __launch_bounds__(RENDER_WG, 4) void k_render(const RenderArgs a) {
 
 extern "C" {
 
-int bcnf_render_frames(const double* ball_pos, const int32_t* cam_index, const double* sigma, int64_t n_frames,
-                       const double* cam_pos, const double* basis, int32_t n_cams, const double* ph_edges,
-                       const double* th_edges, int32_t n_samples, uint64_t seed, uint64_t offset, int64_t first_frame,
-                       void* images, int32_t images_f64, int32_t* counts, int32_t* n_in, void* stream) {
+static int render_launch(const double* ball_pos, const int32_t* cam_index, const double* sigma, int64_t n_frames,
+                         const double* cam_pos, const double* basis, int32_t n_cams, const double* ph_edges,
+                         const double* th_edges, int32_t n_samples, uint64_t seed, uint64_t offset, int64_t first_frame,
+                         const uint32_t* frame_index, void* images, int32_t images_f64, int32_t* counts, int32_t* n_in,
+                         bool lit_only, void* stream) {
   if (n_frames < 0 || n_cams < 0 || n_samples < 0 || first_frame < 0) return BCNF_ERR_ARG;
   if (n_frames == 0) return BCNF_OK;
-  if (first_frame + n_frames > 0x100000000LL || n_frames > 0x7fffffffLL) return BCNF_ERR_UNSUPPORTED;
-  if (!ball_pos || !cam_index || !sigma || !cam_pos || !basis || !ph_edges || !th_edges || !images || n_cams < 1)
+  if ((!frame_index && first_frame + n_frames > 0x100000000LL) || n_frames > 0x7fffffffLL) return BCNF_ERR_UNSUPPORTED;
+  if (!ball_pos || !cam_index || !sigma || !cam_pos || !basis || !ph_edges || !th_edges || n_cams < 1)
     return BCNF_ERR_ARG;
+  if (lit_only ? !n_in : !images) return BCNF_ERR_ARG;
   if (((uintptr_t)images | (uintptr_t)counts) & 15) return BCNF_ERR_ARG;
   RenderArgs a;
   a.ball = ball_pos;
@@ -194,12 +202,40 @@ int bcnf_render_frames(const double* ball_pos, const int32_t* cam_index, const d
   a.off_lo = (uint32_t)offset;
   a.off_hi = (uint32_t)(offset >> 32);
   a.first_frame = (uint32_t)first_frame;
+  a.frame_index = frame_index;
   a.images = images;
   a.counts = counts;
   a.n_in = n_in;
   const dim3 grid((unsigned)n_frames), block(RENDER_WG);
-  return images_f64 ? bcnf_rt::launch<k_render<double>>(grid, block, 0, (hipStream_t)stream, a)
-                    : bcnf_rt::launch<k_render<float>>(grid, block, 0, (hipStream_t)stream, a);
+  if (lit_only) return bcnf_rt::launch<k_render<float, false>>(grid, block, 0, (hipStream_t)stream, a);
+  return images_f64 ? bcnf_rt::launch<k_render<double, true>>(grid, block, 0, (hipStream_t)stream, a)
+                    : bcnf_rt::launch<k_render<float, true>>(grid, block, 0, (hipStream_t)stream, a);
+}
+
+int bcnf_render_frames(const double* ball_pos, const int32_t* cam_index, const double* sigma, int64_t n_frames,
+                       const double* cam_pos, const double* basis, int32_t n_cams, const double* ph_edges,
+                       const double* th_edges, int32_t n_samples, uint64_t seed, uint64_t offset, int64_t first_frame,
+                       void* images, int32_t images_f64, int32_t* counts, int32_t* n_in, void* stream) {
+  return render_launch(ball_pos, cam_index, sigma, n_frames, cam_pos, basis, n_cams, ph_edges, th_edges, n_samples, seed,
+                       offset, first_frame, nullptr, images, images_f64, counts, n_in, false, stream);
+}
+
+int bcnf_render_frames_at(const double* ball_pos, const int32_t* cam_index, const double* sigma, int64_t n_frames,
+                          const double* cam_pos, const double* basis, int32_t n_cams, const double* ph_edges,
+                          const double* th_edges, int32_t n_samples, uint64_t seed, uint64_t offset,
+                          const uint32_t* frame_index, void* images, int32_t images_f64, int32_t* counts, int32_t* n_in,
+                          void* stream) {
+  if (!frame_index && n_frames > 0) return BCNF_ERR_ARG;
+  return render_launch(ball_pos, cam_index, sigma, n_frames, cam_pos, basis, n_cams, ph_edges, th_edges, n_samples, seed,
+                       offset, 0, frame_index, images, images_f64, counts, n_in, false, stream);
+}
+
+int bcnf_render_lit(const double* ball_pos, const int32_t* cam_index, const double* sigma, int64_t n_frames,
+                    const double* cam_pos, const double* basis, int32_t n_cams, const double* ph_edges,
+                    const double* th_edges, int32_t n_samples, uint64_t seed, uint64_t offset, int64_t first_frame,
+                    const uint32_t* frame_index, int32_t* n_in, void* stream) {
+  return render_launch(ball_pos, cam_index, sigma, n_frames, cam_pos, basis, n_cams, ph_edges, th_edges, n_samples, seed,
+                       offset, first_frame, frame_index, nullptr, 0, nullptr, n_in, true, stream);
 }
 
 }  // extern "C"

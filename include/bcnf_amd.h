@@ -37,6 +37,10 @@
  *                           49-56 -> simulation/physics.py:53-160)
  *   bcnf_render_frames   <- camera() per frame of record_trajectory, per camera of generate_data
  *                           (simulation/camera.py:30-150, simulation/sampling.py:366-368)
+ *   bcnf_sample_candidates / bcnf_render_lit / bcnf_render_frames_at
+ *                        <- generate_data's rejection loop (simulation/sampling.py:287-410): the prior draws, the
+ *                           point of impact and the distance filter; the visibility filter's lit frames; the videos
+ *                           of the accepted samples
  */
 #ifndef BCNF_AMD_H
 #define BCNF_AMD_H
@@ -645,6 +649,77 @@ int bcnf_render_frames(const double* ball_pos, const int32_t* cam_index, const d
                        const double* cam_pos, const double* basis, int32_t n_cams, const double* ph_edges,
                        const double* th_edges, int32_t n_samples, uint64_t seed, uint64_t offset, int64_t first_frame,
                        void* images, int32_t images_f64, int32_t* counts, int32_t* n_in, void* stream);
+/* bcnf_render_frames with the draw rule's frame index of frame f given by frame_index[f] (device, uint32, n_frames
+ * entries) instead of first_frame + f: the frames of samples that are not consecutive in the rule (the accepted
+ * candidates of generate_data) in one launch. Everything else as above. */
+int bcnf_render_frames_at(const double* ball_pos, const int32_t* cam_index, const double* sigma, int64_t n_frames,
+                          const double* cam_pos, const double* basis, int32_t n_cams, const double* ph_edges,
+                          const double* th_edges, int32_t n_samples, uint64_t seed, uint64_t offset,
+                          const uint32_t* frame_index, void* images, int32_t images_f64, int32_t* counts, int32_t* n_in,
+                          void* stream);
+/* The lit-frame pass of generate_data's visibility filter (sampling.py:370-372 needs only whether a frame is empty):
+ * the same device code, draws and range test as bcnf_render_frames, writing n_in[f] only -- no histogram, no image.
+ * n_in[f] equals what bcnf_render_frames writes for the same frame. frame_index as in bcnf_render_frames_at, or NULL
+ * for first_frame + f. */
+int bcnf_render_lit(const double* ball_pos, const int32_t* cam_index, const double* sigma, int64_t n_frames,
+                    const double* cam_pos, const double* basis, int32_t n_cams, const double* ph_edges,
+                    const double* th_edges, int32_t n_samples, uint64_t seed, uint64_t offset, int64_t first_frame,
+                    const uint32_t* frame_index, int32_t* n_in, void* stream);
+
+/* ---- Candidates of generate_data (simulation/sampling.py:287-410): sample_ballistic_parameters (sampling.py:156-284),
+ * the runaway and underground tests, calculate_point_of_impact (physics.py:246-276) and accept_traveled_distance
+ * (sampling.py:145-153) for candidates first_candidate .. first_candidate + n_candidates - 1 in one launch, fp64.
+ *
+ * Draw rule (bcnf_amd/generate.py:sample_candidates_host restates it in numpy and is its normative statement).
+ * Slot s of candidate c, attempt t, draws
+ *   (w0, w1, w2, w3) = Philox4x32-10 with
+ *     counter (c low half, c high half, s, t),
+ *     key     (seed low half, seed high half ^ 0x60000000)     -- BCNF_GEN_KEY_TAG: the dropout layers' keys carry
+ *                                                                 0x80000000 / 0x40000000 or neither, the camera's
+ *                                                                 0xC0000000;
+ *   u_i = (w_i + 0.5) 2^-32;
+ *   uniform(lo, hi)  = lo + (hi - lo) u0                                                     (t = 0)
+ *   normal           = sqrt(-2 ln u0) cos(2 pi u1), 2 pi = 6.283185307179586                  (t = 0)
+ *   gamma(k, theta)  = Marsaglia-Tsang without the squeeze: k' = k (k >= 1) or k + 1, d = k' - 1/3, c = 1 / sqrt(9 d);
+ *                      attempt t = 0, 1, ...: x = the normal of (w0, w1), v = (1 + c x)^3; accepted when v > 0 and
+ *                      ln u2 < x^2 / 2 + d - d v + d ln v; the value is d v theta, times u3^(1/k) first when k < 1
+ *                      (u3 of the accepted attempt). t < 1000.
+ * Slots follow the call order of sample_ballistic_parameters for two cameras: 0 x0_xy, 1 phi, 2 x0_z, 3 v0_xy, 4 phi_v,
+ * 5 v0_z, 6 w_xy, 7 phi_w, 8 w_z, 9 a, 10 phi_a, 11 theta_a, 12 g, 13 rho, 14 r_ball, 15 Cd, 16 m, 17 cam_radian,
+ * 18 cam_radius, 19-20 cam_angle, 21-22 cam_heights, 23 the uniform of accept_traveled_distance, 24 that of
+ * accept_visibility. kind[s] / p0[s] / p1[s] (HOST arrays of BCNF_GEN_NSLOT) give slot s's distribution: uniform
+ * (min, max), gaussian (mean, std: the draw is the standard normal, the pair feeds the transformation) or gamma
+ * (shape, scale); transform[s] the reference's expression on the raw draw n: NONE n, SQRT_ABS sqrt(|n|) std + mean,
+ * AFFINE n std + mean, CBRT_ABS cbrt(|n|) std + mean, SQRT sqrt(n).
+ *
+ * params[c][BCNF_GEN_NCOL] (device, float64), in the key order of the reference's dict: 0-2 x0, 3-5 v0, 6-8 g
+ * (0, 0, -g), 9-11 w, 12 b = rho A Cd, 13 m, 14-16 a, 17-18 cam_radian_array (cam1_radian, the drawn one), 19 r,
+ * 20 A = pi r^2, 21 Cd, 22 rho, 23 cam_radius, 24-25 cam_angles, 26-27 cam_heights, 28-29 the two filter uniforms.
+ * code[c]: PENDING, RUNAWAY (g_z + a_z > 0), UNDERGROUND (x0_z < 0) or DISTANCE (accept_traveled_distance said no);
+ * poi[c][3] / distance[c]: the point of impact and its distance to x0, NaN for RUNAWAY / UNDERGROUND. The march is
+ * calculate_point_of_impact's with its default dt = 0.1: the position advances by x + v dt with the velocity at the
+ * start of the interval, the velocity by the Dormand-Prince pair of bcnf_resimulate at (rtol, atol), impact is
+ * x + v (-x.z / v.z) at the first z < 0, and (999, 999, 999) after 120 s or once the velocity is not finite.
+ * With do_filter == 0 every candidate stays PENDING and nothing marches (poi / distance NaN). */
+#define BCNF_GEN_NSLOT 25
+#define BCNF_GEN_NCOL 30
+#define BCNF_GEN_KEY_TAG 0x60000000u
+#define BCNF_GEN_UNIFORM 0
+#define BCNF_GEN_GAUSSIAN 1
+#define BCNF_GEN_GAMMA 2
+#define BCNF_GEN_XF_NONE 0
+#define BCNF_GEN_XF_SQRT_ABS 1
+#define BCNF_GEN_XF_AFFINE 2
+#define BCNF_GEN_XF_CBRT_ABS 3
+#define BCNF_GEN_XF_SQRT 4
+#define BCNF_GEN_PENDING 0
+#define BCNF_GEN_RUNAWAY 1
+#define BCNF_GEN_UNDERGROUND 2
+#define BCNF_GEN_DISTANCE 3
+int bcnf_sample_candidates(const int32_t* kind, const int32_t* transform, const double* p0, const double* p1,
+                           uint64_t seed, int64_t first_candidate, int64_t n_candidates, double cam1_radian,
+                           int32_t do_filter, double rtol, double atol, int32_t max_attempts, double* params,
+                           double* poi, double* distance, int32_t* code, void* stream);
 
 
 const char* bcnf_status_string(int status);
