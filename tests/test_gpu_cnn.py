@@ -4,7 +4,11 @@ gradients), the refused shapes and the fallback, the module against its torch-op
 against the reference's fixture (tests/golden/g18_cnn*.npz), one training-mode pass against float64 with the restated
 masks, TrainStep (captured against eager), a [ConcatenateCondition, CNN, LSTM] step, a trailing camera-parameter
 condition, and sample() with its log-density. Values are held to close(1e-5, 1e-5), gradients to close(1e-4, 1e-4)
-(tests/conftest.py)."""
+(tests/conftest.py).
+
+CONV_CASES reaches every arm of CONV_K_DISPATCH (K = 1 ... 8, three kernels each) and every branch of wgrad_plan,
+k_conv_wgrad's chunk / band / image loops and k_conv_tile's tile x round loop that tests/feature_plans.py registers;
+tests/test_feature_plans_cpu.py enforces both on the CPU, so a case taken out of the list fails there."""
 import copy
 import math
 
@@ -35,7 +39,21 @@ CONV_CASES = [(1, 1, 2, 2, 1, 1, 0, 0),          # a single window
               (2, 10, 8, 8, 15, 5, 1, 1),        # shrinking output
               (33, 3, 6, 70, 4, 3, 0, 2),        # pad_h != pad_w; many images; a wide row
               (1, 32, 5, 5, 32, 8, 7, 7),        # every limit at once
-              (2, 1, 90, 160, 8, 8, 3, 3)]       # the real frame size
+              (2, 1, 90, 160, 8, 8, 3, 3),       # the real frame size
+              # the remaining arms of CONV_K_DISPATCH
+              (2, 3, 9, 12, 5, 2, 1, 0),         # K = 2
+              (2, 6, 10, 13, 9, 4, 3, 2),        # K = 4
+              (2, 7, 11, 9, 12, 6, 5, 2),        # K = 6
+              (2, 4, 9, 14, 6, 7, 3, 6),         # K = 7, pad_w = K - 1
+              # the branches of wgrad_plan / k_conv_wgrad / k_conv_tile (feature_plans.CONV_BRANCHES has the fields)
+              (1025, 1, 4, 5, 3, 2, 0, 1),       # 512 workgroups: workgroup 0 walks three images, the others two
+              (1, 32, 8, 160, 32, 3, 1, 1),      # four x chunks of 42, the last ragged (36); two bands, three passes;
+                                                 # forward tiles (1 x 5) x 2 rounds
+              (1, 32, 8, 50, 32, 5, 2, 2),       # chunk width 25: the window of columns 24, 25 straddles two chunks
+              (1, 32, 15, 16, 32, 3, 1, 1),      # band height 7: the window of rows 6, 7 straddles two bands
+              (1, 32, 40, 24, 32, 8, 7, 7),      # the GWC > K halving: chunks of 16 = 2 K, 12 bands, 8 passes
+              (1, 20, 37, 150, 32, 7, 3, 3)]     # K = 7 at scale: 4 chunks (ragged 28), 9 bands, 5 passes, 5 x 5 tiles
+                                                 # x 2 (forward) and 3 (input gradient) rounds
 
 
 def conv_inputs(case):

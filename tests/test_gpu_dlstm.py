@@ -3,7 +3,11 @@
 VerboseLSTM module against torch's own LSTM, the networks and a full model against the reference's fixture
 (tests/golden/g17_dlstm*.npz), the folded `fc` Linear against the unfolded path, TrainStep (captured against eager, the
 t_DLSTM_large shape, a hybrid step) and sample() with its log-density. Values are held to close(1e-5, 1e-5), gradients
-to close(1e-4, 1e-4) (tests/conftest.py)."""
+to close(1e-4, 1e-4) (tests/conftest.py).
+
+LSTM_CASES reaches all eight arms of LSTM_DISPATCH (H = 16 ... 128), forward and backward, each also in the forward's
+gates = NULL form; tests/test_feature_plans_cpu.py enforces it on the CPU against tests/feature_plans.py, so a case
+taken out of the list fails there."""
 import copy
 import math
 
@@ -45,7 +49,11 @@ LSTM_CASES = [(1, 1, 16, 1),         # a lone row, one step
               (33, 30, 48, 1),       # H not a power of two; three tiles
               (16, 2, 64, 2),        # a full tile
               (5, 30, 128, 2),       # the widest form: 128 weight registers per lane
-              (40, 16, 128, 1)]
+              (40, 16, 128, 1),
+              (17, 3, 80, 2),        # the arms of LSTM_DISPATCH no shipped config takes: H = 80,
+              (5, 4, 96, 1),         # 96
+              (20, 2, 112, 2),       # and 112
+              (3, 1, 32, 2)]         # one step in both directions
 
 
 def lstm_inputs(B, S, H, dirs):
@@ -125,6 +133,13 @@ def test_lstm_kernels_against_float64(B, S, H, dirs):
             ok, err = close(dpv[d].cpu().view(B, S, 4 * H), dp_ref[d], rtol=1e-4, floor=1e-4)
             print(f"dP[{d}] pad={pad} err={err:.3e}")
             assert ok, ("dP", d, pad, err)
+        # the module's no_grad form (gates = cells = NULL) saves nothing and gives the same bits
+        ob, o2 = guarded(rows, dirs * H, ldo)
+        N.call("bcnf_lstm_forward", Pg[0], Pg[rev] if dirs == 2 else None, ldp, Wd[0], Wd[rev] if dirs == 2 else None,
+               bd[0], bd[rev] if dirs == 2 else None, B, S, H, dirs, o2, ldo, None, None, st)
+        torch.cuda.synchronize()
+        assert canaries_alive(ob, rows, dirs * H, ldo), (pad, "out canary, no saves")
+        assert torch.equal(o2, ov), (pad, "out without saves")
 
 
 def against_float64_copy(net, x, what):

@@ -2,7 +2,11 @@
 (bcnf_attn_forward / bcnf_attn_backward) and residual + LayerNorm (bcnf_add_layernorm_*) alone against float64 torch
 restatements, the networks and a full model against the reference's fixture (tests/golden/g16_transformer.npz), the
 folded `output` Linear against the unfolded path, graph-captured TrainStep against eager steps, and sample() with its
-log-density. Values are held to close(1e-5, 1e-5), gradients to close(1e-4, 1e-4) (tests/conftest.py)."""
+log-density. Values are held to close(1e-5, 1e-5), gradients to close(1e-4, 1e-4) (tests/conftest.py).
+
+ATTN_CASES reaches all 2 x 4 arms of ATTN_DISPATCH, and LN_D x LN_ROWS with LN_CAP_CASES all five arms of LN_DISPATCH
+and the LN_MAX_WG cap of ln_plan; tests/test_feature_plans_cpu.py enforces it on the CPU against the restatement in
+tests/feature_plans.py, so a case taken out of a list fails there."""
 import copy
 import math
 
@@ -37,7 +41,13 @@ def attn_f64(q, k, v, heads):
 ATTN_CASES = [(3, 30, 4, 8), (2, 16, 8, 21), (2, 30, 4, 25), (2, 30, 8, 32), (1, 1, 1, 4),
               (3, 30, 1, 16),        # three (sample, head) pairs leave a workgroup partly empty
               (2, 33, 2, 6),         # first S past the two-heads-per-wave form
-              (1, 64, 2, 64)]        # both limits
+              (1, 64, 2, 64),        # both limits
+              # the remaining arms of ATTN_DISPATCH and the edges of its buckets
+              (2, 30, 2, 33),        # <32,64> at its first head_dim
+              (2, 32, 3, 9),         # the last S of the two-slot form; the first head_dim past 8
+              (1, 40, 3, 17),        # <64,32>
+              (1, 64, 1, 16),        # <64,16> at its upper edge
+              (5, 2, 1, 1)]          # head_dim 1
 
 
 @pytest.mark.parametrize("B,S,heads,hd", ATTN_CASES)
@@ -129,16 +139,40 @@ def test_attention_module_fused_equals_torch_ops():
 
 
 # ------------------------------------------------------------------------------------------ residual + LayerNorm
-@pytest.mark.parametrize("d", [6, 16, 100, 168, 256, 1024])
-@pytest.mark.parametrize("rows", [1, 63, 257])
-def test_add_layernorm_against_float64(rows, d):
-    from bcnf_amd import _native as N
+LN_D = [6, 16, 100, 168, 256, 1024,
+        65, 257, 300, 512]           # T = 2 at its first d; T = 8 (257 ... 512) at both ends and inside
+LN_ROWS = [1, 63, 257,
+           9]                        # two workgroups of five and four rows: a wave with two rows, three with one
+LN_CAP_CASES = [(8193, 6), (8193, 100)]      # past LN_MAX_WG workgroups: nine rows each, three for one of the waves
+LN_NULLABLE_CASE = (63, 100)
+
+
+def ln_inputs(rows, d):
     gen = torch.Generator().manual_seed(rows * 2048 + d)
     x = (2.0 * torch.randn(rows, d, generator=gen) + 0.5).float()
     r = torch.randn(rows, d, generator=gen).float()
     gamma = (0.7 + 0.6 * torch.rand(d, generator=gen)).float()
     beta = (0.1 * torch.randn(d, generator=gen)).float()
     dy = torch.randn(rows, d, generator=gen).float()
+    return x, r, gamma, beta, dy
+
+
+@pytest.mark.parametrize("d", LN_D)
+@pytest.mark.parametrize("rows", LN_ROWS)
+def test_add_layernorm_against_float64(rows, d):
+    add_layernorm_against_float64(rows, d)
+
+
+@pytest.mark.parametrize("rows,d", LN_CAP_CASES)
+def test_add_layernorm_past_the_workgroup_cap(rows, d):
+    """More than LN_MAX_WG * LN_MIN_RPW = 8192 rows: the backward's workgroups stay at the cap and take nine rows
+    each (911 workgroups; tests/feature_plans.py), so a wave sums three rows into its column partials."""
+    add_layernorm_against_float64(rows, d)
+
+
+def add_layernorm_against_float64(rows, d):
+    from bcnf_amd import _native as N
+    x, r, gamma, beta, dy = ln_inputs(rows, d)
     eps = 1e-5
     xr, rr, gr, br = (a.double().requires_grad_(True) for a in (x, r, gamma, beta))
     yr = torch.nn.functional.layer_norm(xr + rr, (d,), gr, br, eps)
@@ -171,6 +205,61 @@ def test_add_layernorm_against_float64(rows, d):
     for got, ref, what in ((dxv, xr.grad, "dx"), (dgv.view(-1), gr.grad, "dgamma"), (dbv.view(-1), br.grad, "dbeta")):
         ok, err = close(got.cpu(), ref, rtol=1e-4, floor=1e-4)
         assert ok, (what, err)
+
+
+def test_add_layernorm_nullable_outputs():
+    """What the module passes for frozen parameters and a detached input: beta = NULL on the forward is a zero beta;
+    the backward with dx = NULL, with dgamma only and with dbeta only gives the full call's matching outputs bit for
+    bit, and its partials stay inside `work`."""
+    from bcnf_amd import _native as N
+    rows, d = LN_NULLABLE_CASE
+    x, r, gamma, beta, dy = ln_inputs(rows, d)
+    eps = 1e-5
+    st = N.stream_handle(torch.device(DEV, torch.cuda.current_device()))
+    xd, rd, gd, bd, dyd = (a.to(DEV) for a in (x, r, gamma, beta, dy))
+    wb = N.query_i64("bcnf_add_layernorm_work_bytes", rows, d)
+
+    def forward(b):
+        (yb, yv), (mb, mv), (sb, sv) = guarded(rows, d), guarded(1, rows), guarded(1, rows)
+        N.call("bcnf_add_layernorm_forward", xd, rd, gd, b, rows, d, eps, yv, mv, sv, st)
+        torch.cuda.synchronize()
+        assert canaries_alive(yb, rows, d) and canaries_alive(mb, 1, rows) and canaries_alive(sb, 1, rows)
+        return yv, mv, sv
+
+    def backward(want_dx, want_dg, want_db):
+        outs = [guarded(rows, d) if want_dx else None, guarded(1, d) if want_dg else None,
+                guarded(1, d) if want_db else None]
+        wbuf, wv = guarded(1, wb // 4)
+        N.call("bcnf_add_layernorm_backward", xd, rd, gd, mv, sv, dyd, rows, d,
+               *[None if o is None else o[1] for o in outs], wv, st)
+        torch.cuda.synchronize()
+        for o, shape in zip(outs, ((rows, d), (1, d), (1, d))):
+            assert o is None or canaries_alive(o[0], *shape)
+        # the guards of `work` hold; inside, the partials are written iff a parameter gradient was asked for
+        assert bool(torch.isnan(wbuf[:64]).all()) and bool(torch.isnan(wbuf[64 + wb // 4:]).all())
+        assert bool(torch.isfinite(wv).all()) if want_dg or want_db else bool(torch.isnan(wv).all())
+        return [None if o is None else o[1] for o in outs]
+
+    yv, mv, sv = forward(bd)
+    y0, m0, s0 = forward(None)
+    yz, _, _ = forward(torch.zeros(d, device=DEV))
+    assert torch.equal(y0, yz) and torch.equal(m0, mv) and torch.equal(s0, sv)
+    ok, err = close((yv - y0).cpu(), beta.double().expand(rows, d))
+    assert ok, ("beta", err)
+    dx, dg, db = backward(True, True, True)
+    z = x.double() + r.double()
+    xh = (z - z.mean(-1, keepdim=True)) / torch.sqrt(z.var(-1, unbiased=False, keepdim=True) + eps)
+    for got, ref, what in ((dg.view(-1), (dy.double() * xh).sum(0), "dgamma"), (db.view(-1), dy.double().sum(0), "dbeta")):
+        ok, err = close(got.cpu(), ref, rtol=1e-4, floor=1e-4)
+        assert ok, (what, err)
+    _, dg1, db1 = backward(False, True, True)
+    assert torch.equal(dg1, dg) and torch.equal(db1, db)
+    dx2, dg2, _ = backward(True, True, False)
+    assert torch.equal(dx2, dx) and torch.equal(dg2, dg)
+    dx3, _, db3 = backward(True, False, True)
+    assert torch.equal(dx3, dx) and torch.equal(db3, db)
+    dx4, _, _ = backward(True, False, False)                             # both parameters frozen: no partials at all
+    assert torch.equal(dx4, dx)
 
 
 def test_add_layernorm_outside_the_limit_is_refused_and_falls_back():
