@@ -14,7 +14,9 @@ from bcnf_amd.generate import generate_data, generate_data_device, sample_candid
 from bcnf_amd.render import (camera, camera_basis, get_cams_position, record_trajectory, render_device, render_host,
                              standard_normals, visibility)
 from bcnf_amd.sampling import posterior_mode
+from bcnf_amd.trainer import Trainer, TrainerParameterHistoryHandler
 from bcnf_amd.utils import ParameterIndexMapping, inn_nll_loss, load_config, log_prob_from_latent
+from bcnf_amd.validate import ValidationPass
 
 __all__ = [
     "ActNorm", "CondRealNVP_v2", "ConditionalAffineCouplingLayer", "ConditionalInvertibleLayer",
@@ -25,4 +27,5 @@ __all__ = [
     "posterior_mode", "camera", "record_trajectory", "camera_basis", "get_cams_position", "render_device",
     "render_host", "standard_normals", "visibility", "VideoBatches",
     "generate_data", "generate_data_device", "sample_candidates_host",
+    "Trainer", "TrainerParameterHistoryHandler", "ValidationPass",
 ]

@@ -49,6 +49,7 @@ EXPORTS = (
     "bcnf_lstm_forward", "bcnf_lstm_backward",
     "bcnf_conv_block_forward", "bcnf_conv_block_work_bytes", "bcnf_conv_block_backward",
     "bcnf_render_frames", "bcnf_render_frames_at", "bcnf_render_lit", "bcnf_sample_candidates",
+    "bcnf_validation_stats",
 )
 ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
 MAX_TENSORS = 48
@@ -234,6 +235,7 @@ def _bind(lib):
                                    ctypes.c_uint64, _i64, _vp, _vp, _vp]),
         "bcnf_sample_candidates": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _i64, _i64, ctypes.c_double, _i32,
                                           ctypes.c_double, ctypes.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
+        "bcnf_validation_stats": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _vp, _vp, _vp, _i64, _vp]),
         "bcnf_status_string": (ctypes.c_char_p, [_i32]),
         "bcnf_abi_version": (_i32, []),
     }

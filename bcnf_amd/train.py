@@ -41,6 +41,9 @@ MI355X specifics:
   row per batch of the epoch), so no copy node and, with `run_epoch`, no host sync per step: the epoch's
   steps are replayed back to back and the Trainer's per-batch divergence check (trainer.py:168) runs
   on the device (guard, include/bcnf_amd.h), halting the epoch in the state the reference raises in.
+* the Adam launches take lr by value, so a captured step holds the rate it was captured with: a scheduler's
+  change goes through `set_lr`, which drops the captured graphs for the next step to recapture
+  (bcnf_amd/trainer.py calls it after every scheduler step that moved the rate).
 """
 from __future__ import annotations
 
@@ -569,6 +572,24 @@ class TrainStep:
                     self._bind_grads()
         self._graphs = (g1, g2, vals)
         self._single_grads = [p.grad for p in self.params]   # what .grad shows after a g1 replay
+
+    def set_lr(self, lr: float):
+        """The learning rate of every later step (a scheduler's change, trainer.py:222-227). The Adam launches take
+        lr by value, so a captured graph holds the rate it was captured with and an edit of `opt.param_groups` alone
+        never reaches it: this drops every captured graph, with the gradient bindings that belong to them, and the
+        next step captures again through _build_graphs (whose snapshot / restore undo the warm-up), exactly as the
+        first step did. The optimizer state, the dropout RNG offset, the epoch cursor, the history and the pool are
+        kept; an eager TrainStep only has its param groups edited."""
+        for group in self.opt.param_groups:
+            group["lr"] = float(lr)
+        if self._graphs is None and not self._multi:
+            return
+        self._graphs = None
+        self._multi = {}
+        self._g2_hidden = None
+        self._g21 = None
+        self._single_grads = None
+        self._rebind = False
 
     def step(self, y, traj):
         """One training step; returns (loss, nll, mse) as Python floats (the Trainer's three .item())."""

@@ -29,6 +29,9 @@
  *   bcnf_adam_step       <- optimizer.step() of torch.optim.Adam built by the Trainer (trainer.py:136,270)
  *   bcnf_clip_grad_norm  <- torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1.0)
  *                           (trainer.py:275, after the step)
+ *   bcnf_validation_stats
+ *                        <- Trainer._validate_batch's losses, z.mean(0), z.std(0) (trainer.py:293-303) and the
+ *                           log_det_J.mean() _train logs (trainer.py:217), with the epoch's `val_loss += loss`
  *   bcnf_linear_forward / bcnf_linear_backward
  *                        <- nn.Linear of FullyConnectedFeatureNetwork (feature_network.py:114-145)
  *   bcnf_wide_*          <- the same stack interfaces for the wide-MLP shapes (FC_large / LSTM_large)
@@ -495,6 +498,23 @@ int bcnf_head_mse_backward(const float* x, int64_t ldx, int32_t in_features, con
                            float* dbias, float* dx, int64_t ldd, int32_t accumulate_dx, void* stream);
 int bcnf_hybrid_finalize(float* loss_vals, const void* work, int64_t batch, int32_t out_features, float weight,
                          int32_t* guard, void* stream);
+
+/* ---- Validation statistics (Trainer._validate_batch, trainer.py:279-303, and what _train logs from its last batch,
+ * trainer.py:213-217) ---------------------------------------------------------------------------------------------
+ * z (B x D), ldj (B), pred and y (B x D each; both NULL when hybrid_weight == 0). One launch, one workgroup, writes
+ * the 4 + 2 D floats
+ *   row = [loss, nll, mse, mean(ldj), z.mean(0)[D], z.std(0)[D]]
+ * with nll = mean_b(0.5 sum_d z^2 - ldj), mse = mean((pred - y)^2) (0 without pred), loss = (nll + mse w) / (1 + w)
+ * evaluated in fp32 from the rounded nll and mse, and z.std the unbiased estimate (NaN at B = 1, as torch.std). Every
+ * sum is fp64 in an order fixed by (B, D) -- no atomics; same inputs, same bits -- and the deviations are a second pass
+ * around the fp64 mean. epoch_sum (3 doubles, nullable): after the row is written one thread adds (loss, nll, mse) as
+ * doubles, so launches of one stream accumulate in batch order like the Trainer's `val_loss += loss`. cursor
+ * (nullable; an epoch cursor of bcnf_gather_batch): the row is written at row + cursor[0] * (4 + 2 D) and the cursor
+ * then advanced modulo n_batches, the last thing the launch does. 1 <= D <= 32 (else BCNF_ERR_UNSUPPORTED), B >= 1,
+ * w >= 0 and finite; nothing is launched on a bad argument. */
+int bcnf_validation_stats(const float* z, const float* ldj, const float* pred, const float* y, int64_t batch,
+                          int32_t size, float weight, float* row, double* epoch_sum, int64_t* cursor,
+                          int64_t n_batches, void* stream);
 
 /* ---- Transformer feature networks (feature_network.py:183-307: MultiHeadAttention, TransformerBlock) ---------------
  * The two pieces of a block that are not a Linear layer. fp32, stream-ordered, stateless; every sum runs in a fixed
