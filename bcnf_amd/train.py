@@ -44,6 +44,9 @@ MI355X specifics:
 * the Adam launches take lr by value, so a captured step holds the rate it was captured with: a scheduler's
   change goes through `set_lr`, which drops the captured graphs for the next step to recapture
   (bcnf_amd/trainer.py calls it after every scheduler step that moved the rate).
+
+This module holds the step itself; the device pool with its epoch walk and graph schedule live in bcnf_amd/epoch.py
+(shared with the validation pass), the data-parallel gradient bucket in bcnf_amd/bucket.py.
 """
 from __future__ import annotations
 
@@ -54,6 +57,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from bcnf_amd.bucket import GradBucket
+from bcnf_amd.epoch import DevicePool, EpochWalk, check_indices, graph_schedule
 from bcnf_amd.errors import TrainingDivergedError
 from bcnf_amd.optim import FusedAdam, clip_grad_norm_
 from bcnf_amd.utils import inn_nll_loss
@@ -103,6 +108,21 @@ class _PackedParameters:
         self.param.grad = self.flat_grad
 
 
+class _Captured:
+    """The captured step: its static input buffers, its graphs and the gradient buffers they own. set_lr drops it."""
+
+    def __init__(self, y, traj, idx):
+        self.y, self.traj, self.idx = y, traj, idx      # static inputs (idx: step_indexed's; None for step())
+        self.g1 = None          # the step (world > 1: up to the bucket pack; the all-reduce follows, then g2)
+        self.vals = None        # g1's logged (loss, nll, mse)
+        self.g2 = None          # data parallel: the update segment
+        self.g2_hidden = None   # data parallel: update segment without the (unobservable) clip
+        self.g21 = None         # data parallel: hidden update + the next step's forward/backward, one graph
+        self.single_grads = None   # what .grad shows after a g1 replay
+        self.multi = {}         # steps -> (graph, grads): run_epoch's multi-step graphs (world 1)
+        self.rebind = False     # .grad currently points at buffers other than the single-step graph's
+
+
 class TrainStep:
     def __init__(self, model, lr: float = 2e-4, hybrid_weight: float = 0.0, capture: bool = True,
                  max_norm: float = 1.0, process_group=None, overlap_ranges: int = 0):
@@ -133,30 +153,16 @@ class TrainStep:
         self.fused_loss = self.hybrid_weight == 0.0
         self._cot_stack = None
         self._cot = None
-        self._graphs = None
-        self._static = None
-        self._pool = None
-        self._multi = {}        # steps -> (graph, steps, grads): run_epoch's multi-step graphs (world 1)
-        self._single_grads = None
-        self._rebind = False    # .grad currently points at buffers other than the single-step graph's
-        self._book = None       # Adam's finished-workgroup counter (bcnf_adam_step_bookkeep)
-        self._g2_hidden = None  # data parallel: update segment without the (unobservable) clip
-        self._g21 = None        # data parallel: hidden update + the next step's forward/backward, one graph
-        self._cond_shape = None  # (per-sample condition shape, its size) when the pool rows are padded
-        self._epoch = None      # (order, cursor, n_batches, batch) for the device-cursor batch walk
-        self._bucket = None     # data parallel: every gradient in one buffer, one all-reduce per step
-        self._n_grad = 0        # gradient floats in the bucket; the 3 logged values follow (reduced with them)
-        self._gvals = None      # data parallel: the all-reduced (loss, nll, mse) -- a view of the bucket tail
-        self._packed_inplace = False   # the last bucket pack found the gradients already in place
-        self._host_cursor = 0   # host mirror of the epoch cursor (the history row of the next step)
+        self._cap = None        # the captured step (_Captured); None until the first captured step and after set_lr
+        self.pool = None        # DevicePool (set_pool)
+        self.walk = None        # EpochWalk over the pool (set_epoch): the device-cursor batch walk
+        # data parallel: every gradient in one buffer, one all-reduce per step
+        self.bucket = GradBucket(self.params, process_group, self.world) if self.world > 1 else None
         self.last_clip_norm = None   # device scalar: total gradient norm before the last observable clip
         # data parallel, wide family: the backward runs in `overlap_ranges` block ranges and each finished range's
         # bucket slice is all-reduced (async) while the rest of the backward runs; eager steps (the collectives are
         # issued between kernel launches, outside any captured graph), joined before the update
         self.overlap_ranges = 0
-        self._works = []        # in-flight all-reduces of bucket slices, and the slices [lo, hi) they cover
-        self._reduced = []
-        self._hooks = None      # data parallel: the stack attributes _stack_hooks installs around each backward
         from bcnf_amd.wide import WideStack
         if self.world > 1 and overlap_ranges > 0 and isinstance(getattr(model, "fused", None), WideStack):
             self.overlap_ranges = min(int(overlap_ranges), model.fused.cfg.n_blocks)
@@ -171,8 +177,10 @@ class TrainStep:
             self._side = torch.cuda.Stream(device=dev)
         self._guard = None
         self._hist = None
+        self._book = None       # Adam's finished-workgroup counter (bcnf_adam_step_bookkeep)
         if dev.type == "cuda":
             self._guard = torch.zeros(GUARD_WORDS, dtype=torch.int32, device=dev)
+            self._book = torch.zeros(1, dtype=torch.int32, device=dev)
             model.fused.guard = self._guard
             self._hist = torch.zeros((1, 3), dtype=torch.float32, pin_memory=True)
 
@@ -183,7 +191,8 @@ class TrainStep:
                 raise RuntimeError("bcnf_amd TrainStep: the model's feature-network parameters were replaced (moved or "
                                    "cast) after this TrainStep packed them; build a new TrainStep")
             self._packed.clear()
-        with self._stack_hooks(), self._side_overlap():
+        hooks = self.bucket.stack_hooks(self.model.fused) if self.bucket is not None else contextlib.nullcontext()
+        with hooks, self._side_overlap():
             vals = self._forward_backward_body(y, traj, gather, adam)
         if self._packed is not None:
             self._packed.gather()
@@ -215,25 +224,22 @@ class TrainStep:
         if self.fused_loss:
             # reduced in the backward launch; a deferred gather runs inside the pack launch
             vals = self.model.nll_loss(y, traj, defer_reduction=True, gather=gather)
-            if self._cot is None or self._cot.device != vals.device:
-                self._cot = torch.tensor([1.0, 0.0, 0.0], device=vals.device)
+            cot = self._cotangent(vals.device)
             if adam is not None:                          # the optimizer step, inside the folded backward tail
                 self.model.fused.pending_adam = adam(vals)
-            torch.autograd.backward(vals, self._cot)      # loss.backward()
+            torch.autograd.backward(vals, cot)            # loss.backward()
             if adam is not None and self.model.fused.pending_adam is not None:
                 self.model.fused.pending_adam = None
                 raise RuntimeError("bcnf_amd TrainStep: the folded backward did not take the fused Adam update")
             return vals.detach()
         if self.hybrid:
             vals = self.model.hybrid_loss(y, traj, hybrid_weight=self.hybrid_weight, defer_reduction=True)
-            if self._cot is None or self._cot.device != vals.device:
-                self._cot = torch.tensor([1.0, 0.0, 0.0], device=vals.device)
-                self._cot_stack = torch.tensor([1.0 / (1.0 + self.hybrid_weight), 0.0, 0.0], device=vals.device)
+            cot = self._cotangent(vals.device)
             st = self.model.fused
-            st.hybrid_cot = (self._cot, self._cot_stack, self.hybrid_weight)
-            st.hybrid_judge = self.world == 1       # data parallel: the all-reduced loss is judged (_check_global)
+            st.hybrid_cot = (cot, self._cot_stack, self.hybrid_weight)
+            st.hybrid_judge = self.world == 1       # data parallel: the all-reduced loss is judged (check_global)
             try:
-                torch.autograd.backward(vals, self._cot)      # loss.backward()
+                torch.autograd.backward(vals, cot)            # loss.backward()
             finally:
                 st.hybrid_cot = None
                 st.hybrid_judge = True
@@ -245,171 +251,29 @@ class TrainStep:
         loss.backward()
         return torch.stack([loss.detach(), nll.detach(), mse.detach()])
 
-    def _pack_grads(self):
-        """All gradients -> one contiguous bucket, so the data-parallel exchange is ONE collective per step whatever
-        the number of feature-network tensors (FC_large: 17, LSTM_large: 19). Gradients the backward already wrote
-        into their bucket slots (the folded backwards, FusedStack / WideStack.grad_bucket) are not copied."""
-        grads = [p.grad for p in self.params]
-        if any(g is None for g in grads):
-            raise RuntimeError("bcnf_amd TrainStep: a parameter received no gradient")
-        if self._bucket is None:
-            self._alloc_bucket(grads[0].device)
-        base, off, slots = self._bucket.data_ptr(), 0, []
-        for g in grads:
-            slots.append((g, off, g.is_contiguous() and g.data_ptr() == base + 4 * off))
-            off += g.numel()
-        self._packed_inplace = all(ok for _, _, ok in slots)
-        if self._packed_inplace:
-            return
-        if not any(ok for _, _, ok in slots):
-            torch.cat([g.reshape(-1) for g in grads], out=self._bucket[:self._n_grad])
-            return
-        for g, o, ok in slots:
-            if ok:
-                continue
-            if any(lo < o + g.numel() and o < hi for lo, hi in self._reduced):
-                raise RuntimeError("bcnf_amd TrainStep: a gradient of an already all-reduced bucket slice is not in "
-                                   "its slot")
-            self._bucket[o:o + g.numel()].copy_(g.reshape(-1))
-
-    def _alloc_bucket(self, dev):
-        """The gradient bucket + a 4-float tail holding the step's logged (loss, nll, mse): the one all-reduce of the
-        step also averages them, so every rank logs -- and judges divergence on -- the global loss."""
-        self._n_grad = sum(p.numel() for p in self.params)
-        self._bucket = torch.zeros(self._n_grad + 4, dtype=torch.float32, device=dev)
-        self._gvals = self._bucket[self._n_grad:self._n_grad + 3]
-
-    def _setup_bucket(self):
-        """Data parallel: allocate the gradient bucket up front and let the folded backwards write their gradients
-        into it (no copy before the all-reduce): the small family's (coupling + feature Linear,
-        FusedStack.grad_bucket), the wide family's coupling gradients (WideStack.grad_bucket), the latter range by
-        range when overlap_ranges is set. The stack hooks are installed only around this step's own backward
-        (_stack_hooks), so a backward outside the TrainStep never writes into the bucket or issues collectives."""
-        if self.world == 1 or self._bucket is not None:
-            return
-        self._alloc_bucket(self.params[0].device)
-        lin = self.model._fold_linear() if hasattr(self.model, "_fold_linear") else None
-        if lin is None or not self.fused_loss or self.layerwise:
-            return
-        offs, off = {}, 0
-        for p in self.params:
-            offs[id(p)] = off
-            off += p.numel()
-        fp = self.model.fused.flat_param
-        from bcnf_amd.wide import WideStack
-        if isinstance(self.model.fused, WideStack):
-            if id(fp) not in offs:
-                return
-            st = self.model.fused
-            hooks = {"grad_bucket": (self._bucket, offs[id(fp)])}
-            if self.overlap_ranges > 0:
-                nb, r = st.cfg.n_blocks, self.overlap_ranges
-                cuts = [round(nb * i / r) for i in range(r + 1)]
-                hooks["range_blocks"] = [(cuts[i - 1], cuts[i]) for i in range(r, 0, -1) if cuts[i] > cuts[i - 1]]
-                hooks["on_range"] = self._reduce_range
-            self._hooks = hooks
-            return
-        if len(self.params) != (3 if lin.bias is not None else 2) or id(fp) not in offs or id(lin.weight) not in offs:
-            return
-        self._hooks = {"grad_bucket": (self._bucket, (offs[id(fp)], offs[id(lin.weight)],
-                                                      offs[id(lin.bias)] if lin.bias is not None else 0))}
-
-    @contextlib.contextmanager
-    def _stack_hooks(self):
-        """The bucket / range hooks on the fused stack for the duration of this step's forward + backward (eager or
-        being captured), removed afterwards even when the step raises."""
-        st = self.model.fused
-        if not self._hooks:
-            yield
-            return
-        for k, v in self._hooks.items():
-            setattr(st, k, v)
-        try:
-            yield
-        finally:
-            for k in self._hooks:
-                setattr(st, k, None)
-
-    def _drain_slices(self):
-        """Join and forget slice all-reduces a previous step left in flight (it raised between issuing them and the
-        update's join), so this step neither skips those slices nor waits on stale handles."""
-        works, self._works = self._works, []
-        self._reduced.clear()
-        for w in works:
-            try:
-                w.wait()
-            except Exception:       # the failed step's own error was already raised to the caller
-                pass
-
-    def _bind_grads(self):
-        """Every .grad becomes a view of the (reduced) bucket: Adam and the clip read it in place."""
-        off = 0
-        for p in self.params:
-            n = p.numel()
-            p.grad = self._bucket[off:off + n].view_as(p)
-            off += n
-
-    def _reduce_bucket(self):
-        """Sum over ranks of the gradient bucket: ONE RCCL all-reduce per step (the 1/world scaling runs inside
-        the captured update segment, _scale_bucket). With slices already in flight (overlap_ranges), the rest of the
-        bucket -- the feature-network gradients and the logged values -- then a join on every slice."""
-        if not self._works:
-            dist.all_reduce(self._bucket, op=dist.ReduceOp.SUM, group=self.pg)
-            return
-        lo = 0
-        for a, b in sorted(self._reduced) + [(self._bucket.numel(), self._bucket.numel())]:
-            if a > lo:
-                dist.all_reduce(self._bucket[lo:a], op=dist.ReduceOp.SUM, group=self.pg)
-            lo = max(lo, b)
-        for w in self._works:
-            w.wait()
-        self._works.clear()
-        self._reduced.clear()
-
-    def _reduce_range(self, lo: int, hi: int):
-        """A finished block range's bucket slice [lo, hi): its all-reduce runs while the backward continues
-        (WideStack.on_range); the update joins it (_reduce_bucket)."""
-        self._works.append(dist.all_reduce(self._bucket[lo:hi], op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
-        self._reduced.append((lo, hi))
-
-    def _scale_bucket(self):
-        self._bucket.mul_(1.0 / self.world)
-
-    def _allreduce(self, vals=None):
-        """Eager data-parallel exchange; returns the all-reduced logged values (or `vals` at world 1)."""
-        if self.world == 1:
-            return vals
-        self._pack_grads()
-        if vals is not None:
-            self._gvals.copy_(vals)
-        self._reduce_bucket()
-        self._scale_bucket()
-        self._bind_grads()
-        return self._gvals if vals is not None else None
-
-    def _check_global(self):
-        """Data parallel: the divergence guard judged on the all-reduced loss (bcnf_guard_check_global)."""
-        if self.world == 1 or self._guard is None:
-            return
-        from bcnf_amd import _native as N
-        N.call("bcnf_guard_check_global", self._gvals, self._guard, N.stream_handle(self._gvals.device))
+    def _cotangent(self, dev):
+        """d(loss) / d(loss, nll, mse) for loss.backward() on the three logged values; the hybrid step also keeps the
+        coupling stack's share of it, 1 / (1 + w)."""
+        if self._cot is None or self._cot.device != dev:
+            self._cot = torch.tensor([1.0, 0.0, 0.0], device=dev)
+            if self.hybrid:
+                self._cot_stack = torch.tensor([1.0 / (1.0 + self.hybrid_weight), 0.0, 0.0], device=dev)
+        return self._cot
 
     def _update(self, vals=None, clip: bool = True, epoch_book: bool = True):
         """Adam, then clip_grad_norm_ after the step (trainer.py:273-275); the clip launch also advances the
         Adam step count and, in epoch mode, the batch cursor, and stores the logged values into the pinned
         history (end-of-step bookkeeping, no extra launch). epoch_book=False: a batch from outside the epoch
         order (step_indexed while an order is set) -- no cursor advance and no history row."""
-        if self.world > 1 and vals is not None:
-            vals = self._gvals              # every rank logs the global values and halts on the same step
-            self._check_global()
-        cursor = (self._epoch[1], self._epoch[2]) if (self._epoch is not None and epoch_book) else None
+        if self.bucket is not None and vals is not None:
+            vals = self.bucket.gvals        # every rank logs the global values and halts on the same step
+            self.bucket.check_global(self._guard)
+        cursor = self._cursor() if epoch_book else None
         log = (vals, self._hist) if (vals is not None and self._hist is not None and epoch_book) else None
         if not clip:
             # a step inside a multi-step graph that the next step's backward follows: its clip-after-step
             # would only scale gradients that are overwritten before anyone can read them (the reference
             # discards the norm), so Adam's last workgroup does the step's bookkeeping and no clip runs
-            if self._book is None:
-                self._book = torch.zeros(1, dtype=torch.int32, device=self.params[0].device)
             self.opt.step(guard=self._guard, bookkeep=(cursor, log, self._book))
             return
         if self.layerwise:
@@ -433,57 +297,38 @@ class TrainStep:
                 dist.broadcast(p.data, src=src, group=self.pg)
 
     # ------------------------------------------------------------------ eager / graph
-    def eager_step(self, y, traj, gather=None, epoch_book: bool = True):
-        self._drain_slices()
-        self._setup_bucket()
-        vals = self._forward_backward(y, traj, gather)
-        vals = self._allreduce(vals)
-        self._update(vals, epoch_book=epoch_book)
-        self._rebind = self._graphs is not None     # .grad now holds this step's buffers, not a graph's
-        # world > 1: vals is a view of the bucket tail, which the next step overwrites
-        return vals.clone() if self.world > 1 else vals
+    def _cursor(self):
+        """(device cursor, modulo) for the launch that ends a step to advance, in epoch mode."""
+        return (self.walk.cursor, self.walk.n_batches) if self.walk is not None else None
 
-    def _gather(self, defer: bool = False):
-        """Pool rows of the current batch, both tensors in one native launch: the static index buffer, or
-        (epoch mode) batch `cursor` of the device-resident epoch order, the cursor advancing on the device.
+    def _setup_bucket(self):
+        self.bucket.setup(self.model, self.fused_loss and not self.layerwise, self.overlap_ranges)
+
+    def eager_step(self, y, traj, gather=None, epoch_book: bool = True):
+        if self.bucket is not None:
+            self.bucket.drain_slices()
+            self._setup_bucket()
+        vals = self._forward_backward(y, traj, gather)
+        if self.bucket is not None:
+            vals = self.bucket.allreduce(vals)
+        self._update(vals, epoch_book=epoch_book)
+        if self._cap is not None:
+            self._cap.rebind = True     # .grad now holds this step's buffers, not a graph's
+        # world > 1: vals is a view of the bucket tail, which the next step overwrites
+        return vals.clone() if self.bucket is not None else vals
+
+    def _gather(self, idx=None, defer: bool = False):
+        """Pool rows of the current batch, both tensors in one native launch: by the index buffer `idx`, or (epoch
+        mode) batch `cursor` of the device-resident epoch order, the cursor advancing on the device.
         defer=True returns (y, traj, spec): when the step takes the folded path, spec is the gather (not yet
         launched) for the pack launch to run (bcnf_pack_params_fold), else None and the gather has run."""
-        from bcnf_amd import _native as N
-        py, pt = self._pool
-        n = self._epoch[3] if self._epoch is not None else self._static[2].shape[0]
-        y = torch.empty((n,) + tuple(py.shape[1:]), dtype=py.dtype, device=py.device)
-        t = torch.empty((n,) + tuple(pt.shape[1:]), dtype=pt.dtype, device=pt.device)
-        cy = py[0].numel()
-        ct = pt[0].numel()
+        pool, walk = self.pool, self.walk
+        out = pool.empty_batch(walk.batch if walk is not None else idx.shape[0])
         if defer and self.fused_loss and self.fuse_gather and not self.layerwise and \
-                self.model._foldable_linear(y, (self._unpad(t),)) is not None:
-            epoch = self._epoch is not None
-            spec = N.BcnfGather2(idx=(self._epoch[0] if epoch else self._static[2]).data_ptr(),
-                                 cursor=self._epoch[1].data_ptr() if epoch else None, n=n,
-                                 src0=py.data_ptr(), cols0=cy, dst0=y.data_ptr(),
-                                 src1=pt.data_ptr(), cols1=ct, dst1=t.data_ptr())
-            return y, self._unpad(t), spec
-        st = N.stream_handle(py.device)
-        if self._epoch is not None:
-            order, cursor = self._epoch[0], self._epoch[1]
-            N.call("bcnf_gather_batch", order, cursor, n, py, cy, y, pt, ct, t, st)
-        else:
-            N.call("bcnf_gather_rows2", self._static[2], n, py, cy, y, pt, ct, t, st)
-        if defer:
-            return y, self._unpad(t), None
-        return y, self._unpad(t)
-
-    def _unpad(self, t):
-        """A batch of the padded condition pool as the (n, *cond_shape) view the model expects (row stride = the
-        padded width; the folded path reads it in place with float4 loads)."""
-        if self._cond_shape is None:
-            return t
-        shape, X = self._cond_shape
-        return t[:, :X].view((t.shape[0],) + shape)
-
-    def _pool_rows(self, idx):
-        py, pt = self._pool
-        return py.index_select(0, idx), self._unpad(pt.index_select(0, idx))
+                self.model._foldable_linear(out[0], (pool.unpad(out[1]),)) is not None:
+            return walk.gather_spec(out) if walk is not None else pool.gather_spec(idx, idx.shape[0], out=out)
+        y, t = walk.gather(out) if walk is not None else pool.gather_rows(idx, out)
+        return (y, t, None) if defer else (y, t)
 
     def _snapshot(self):
         with torch.no_grad():
@@ -491,14 +336,14 @@ class TrainStep:
             opt = {id(p): {k: v.clone() for k, v in st.items() if torch.is_tensor(v)}
                    for p, st in self.opt.state.items()}
             rng = self.model.fused.rng_state().clone()
-            cur = self._epoch[1].clone() if self._epoch is not None else None
+            cur = self.walk.cursor.clone() if self.walk is not None else None
         return params, opt, rng, cur
 
     def _restore(self, snap):
         params, opt, rng, cur = snap
         with torch.no_grad():
             if cur is not None:
-                self._epoch[1].copy_(cur)
+                self.walk.cursor.copy_(cur)
             for p, v in zip(self.model.parameters(), params):
                 p.copy_(v)
             for p, st in self.opt.state.items():
@@ -511,9 +356,11 @@ class TrainStep:
     def _build_graphs(self, y, traj, idx=None, warmup: int = 2):
         """Warm up (allocations, kernel attributes) on a side stream, undo the warm-up's updates, then
         capture: the first step() applies exactly one update, like every later one."""
-        self._setup_bucket()
-        self._static = (y.clone(), traj.clone(), None if idx is None else idx.clone())
-        sy, st, _ = self._static
+        bucket = self.bucket
+        if bucket is not None:
+            self._setup_bucket()
+        cap = _Captured(y.clone(), traj.clone(), None if idx is None else idx.clone())
+        sy, st = cap.y, cap.traj
         indexed = idx is not None
         snap = self._snapshot()
         s = torch.cuda.Stream()
@@ -521,7 +368,7 @@ class TrainStep:
         with torch.cuda.stream(s):
             for _ in range(warmup):
                 if indexed:
-                    self.eager_step(*self._gather(defer=True))
+                    self.eager_step(*self._gather(cap.idx, defer=True))
                 else:
                     self.eager_step(sy, st)
             self._restore(snap)
@@ -529,49 +376,46 @@ class TrainStep:
         self.opt.zero_grad(set_to_none=True)
         # the three logged values are stored into the pinned history by the clip launch: the host reads
         # them after a stream sync, without a device-to-host copy node
-        g1 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1):
+        cap.g1 = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(cap.g1):
             spec = None
             if indexed:
-                sy, st, spec = self._gather(defer=True)
-            vals = self._forward_backward(sy, st, spec)
-            if self.world == 1:
+                sy, st, spec = self._gather(cap.idx, defer=True)
+            vals = cap.vals = self._forward_backward(sy, st, spec)
+            if bucket is None:
                 self._update(vals)
             else:
-                self._pack_grads()          # the bucket copy is part of the captured step
-                self._gvals.copy_(vals)     # the logged values travel with the gradients
-        g2 = None
-        if self.world > 1:
-            self._bind_grads()              # the update reads the reduced bucket
-            g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2):
-                self._scale_bucket()
+                bucket.pack_grads()         # the bucket copy is part of the captured step
+                bucket.gvals.copy_(vals)    # the logged values travel with the gradients
+        if bucket is not None:
+            bucket.bind_grads()             # the update reads the reduced bucket
+            cap.g2 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(cap.g2):
+                bucket.scale()
                 self._update(vals)
             # the update segment of a step whose clip-after-step is unobservable (every run_epoch step but the
             # last: the next step's backward overwrites the gradients): Adam with the bookkeeping, no clip launch
             if self.skip_hidden_clips and self.opt.can_bookkeep():
-                if self._book is None:
-                    self._book = torch.zeros(1, dtype=torch.int32, device=self.params[0].device)
-                self._g2_hidden = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._g2_hidden):
-                    self._scale_bucket()
+                cap.g2_hidden = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(cap.g2_hidden):
+                    bucket.scale()
                     self._update(vals, clip=False)
                 if indexed:
                     # step i's hidden update and step i+1's gather / forward / backward / bucket in ONE graph: one
                     # inter-graph idle per step instead of two (run_epoch); step i+1's logged values are copied
                     # into g1's buffer, which every update segment logs from
-                    self._g21 = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._g21):
-                        self._scale_bucket()
+                    cap.g21 = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(cap.g21):
+                        bucket.scale()
                         self._update(vals, clip=False)
-                        sy2, st2, spec2 = self._gather(defer=True)
+                        sy2, st2, spec2 = self._gather(cap.idx, defer=True)
                         vals2 = self._forward_backward(sy2, st2, spec2)
-                        self._pack_grads()
-                        self._gvals.copy_(vals2)
+                        bucket.pack_grads()
+                        bucket.gvals.copy_(vals2)
                         vals.copy_(vals2)
-                    self._bind_grads()
-        self._graphs = (g1, g2, vals)
-        self._single_grads = [p.grad for p in self.params]   # what .grad shows after a g1 replay
+                    bucket.bind_grads()
+        cap.single_grads = [p.grad for p in self.params]   # what .grad shows after a g1 replay
+        self._cap = cap
 
     def set_lr(self, lr: float):
         """The learning rate of every later step (a scheduler's change, trainer.py:222-227). The Adam launches take
@@ -582,14 +426,7 @@ class TrainStep:
         kept; an eager TrainStep only has its param groups edited."""
         for group in self.opt.param_groups:
             group["lr"] = float(lr)
-        if self._graphs is None and not self._multi:
-            return
-        self._graphs = None
-        self._multi = {}
-        self._g2_hidden = None
-        self._g21 = None
-        self._single_grads = None
-        self._rebind = False
+        self._cap = None
 
     def step(self, y, traj):
         """One training step; returns (loss, nll, mse) as Python floats (the Trainer's three .item())."""
@@ -607,10 +444,10 @@ class TrainStep:
     def step_async(self, y, traj):
         if not self.capture:
             return self.eager_step(y, traj)
-        if self._graphs is None:
+        if self._cap is None:
             self._build_graphs(y, traj)
-        sy, st, _ = self._static
-        if sy is None or y.shape != sy.shape or traj.shape != st.shape:
+        sy, st = self._cap.y, self._cap.traj
+        if y.shape != sy.shape or traj.shape != st.shape:
             # a batch of another size (the DataLoader's last, drop_last=False): the captured graph holds buffers of
             # the first batch's size, so this one runs eagerly on the same kernels and optimizer state
             return self.eager_step(y, traj)
@@ -621,91 +458,56 @@ class TrainStep:
     # ------------------------------------------------------------------ device-resident data pool
     def set_pool(self, y_pool, traj_pool):
         """Serve batches by index from device-resident tensors (the gather becomes part of the graph)."""
-        if self._graphs is not None:
+        if self._cap is not None:
             raise RuntimeError("set_pool() must precede the first step")
-        for t in (y_pool, traj_pool):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise ValueError("set_pool: contiguous fp32 device tensors required")
         # the folded feature Linear (cnf.py fold_pool_width) reads x rows with float4 loads when they are 16-byte
-        # aligned: zero-pad the pool's rows (90 -> 92 floats for FC_small) once, here
-        self._cond_shape = None
+        # aligned: the pool zero-pads its rows (90 -> 92 floats for FC_small) once, here
         w = self.model.fold_pool_width(traj_pool) if hasattr(self.model, "fold_pool_width") else None
-        if w is not None:
-            X = traj_pool[0].numel()
-            padded = torch.zeros((traj_pool.shape[0], w), dtype=traj_pool.dtype, device=traj_pool.device)
-            padded[:, :X] = traj_pool.reshape(traj_pool.shape[0], X)
-            self._cond_shape = (tuple(traj_pool.shape[1:]), X)
-            traj_pool = padded
-        self._pool = (y_pool, traj_pool)
+        self.pool = DevicePool(y_pool, traj_pool, row_width=w)
 
     def step_indexed(self, idx):
         """step(pool_y[idx], pool_traj[idx]) with the gather captured in the graph."""
-        if self._pool is None:
+        if self.pool is None:
             raise RuntimeError("step_indexed() needs set_pool()")
-        self._check_indices(idx)
-        idx = idx.to(device=self._pool[0].device, dtype=torch.int64).contiguous()
-        if self._epoch is not None:
+        check_indices(idx, self.pool.n)
+        idx = idx.to(device=self.pool.device, dtype=torch.int64).contiguous()
+        if self.walk is not None:
             # a batch outside the epoch order (the ragged remainder of an epoch, drop_last=False): the epoch graphs
             # walk the device cursor and write history rows, so this one runs eagerly on the same kernels and
             # optimizer state without touching the cursor or the history
-            return tuple(self.eager_step(*self._pool_rows(idx), epoch_book=False).tolist())
+            return tuple(self.eager_step(*self.pool.rows(idx), epoch_book=False).tolist())
         if not self.capture:
-            self._static = (None, None, idx)
-            return tuple(self.eager_step(*self._gather()).tolist())
-        if self._graphs is None:
-            self._build_graphs(*self._pool_rows(idx), idx=idx)
-        if self._static[2] is None or idx.shape != self._static[2].shape:
-            return tuple(self.eager_step(*self._pool_rows(idx)).tolist())     # another batch size: eager
-        self._static[2].copy_(idx, non_blocking=True)
+            return tuple(self.eager_step(*self._gather(idx)).tolist())
+        if self._cap is None:
+            self._build_graphs(*self.pool.rows(idx), idx=idx)
+        if self._cap.idx is None or idx.shape != self._cap.idx.shape:
+            return tuple(self.eager_step(*self.pool.rows(idx)).tolist())     # another batch size: eager
+        self._cap.idx.copy_(idx, non_blocking=True)
         self._replay()
         return self._host_values()
-
-    def _check_indices(self, idx):
-        """Pool indices in range (the reference's DataLoader raises IndexError; the device gather would read out of
-        bounds), before anything is launched. Host indices (a DataLoader's) are checked on the host, no device sync;
-        device-resident indices cost one host round trip."""
-        if idx.numel() == 0:
-            return
-        lo, hi = torch.aminmax(idx if idx.device.type == "cpu" else idx.to(torch.int64))
-        n = self._pool[0].shape[0]
-        if int(lo) < 0 or int(hi) >= n:
-            raise IndexError(f"bcnf_amd TrainStep: batch index out of range [0, {n}) (got {int(lo)}..{int(hi)})")
 
     # ------------------------------------------------------------------ device-resident epoch order
     def set_epoch(self, order, batch: int):
         """Walk `order` (device int64, n_batches * batch pool indices, e.g. concatenated shuffled epochs)
         batch by batch with step_epoch(); the graph reads batch `cursor` and advances the cursor itself, so
         a step needs no host-to-device traffic. A later call replaces the order (same size) and rewinds."""
-        if self._pool is None:
+        if self.pool is None:
             raise RuntimeError("set_epoch() needs set_pool()")
         order = order.to(dtype=torch.int64).contiguous()
-        nb = order.numel() // batch
-        if nb < 1 or order.numel() != nb * batch:
-            # whole batches only: a ragged last batch (drop_last=False) goes through step_indexed, which runs a
-            # batch of another size eagerly
-            raise ValueError(f"set_epoch: order must hold a whole number of batches ({order.numel()} indices, "
-                             f"batch {batch}); pass the remainder to step_indexed()")
-        self._check_indices(order)
-        if self._epoch is None:
-            if self._graphs is not None:
-                raise RuntimeError("set_epoch() must precede the first step of a non-epoch TrainStep")
-            dev = order.device
-            self._epoch = (order.clone(), torch.zeros(1, dtype=torch.int64, device=dev), nb, batch)
-            self._hist = torch.zeros((nb, 3), dtype=torch.float32, pin_memory=True)
-        else:
-            o, cursor, nb0, b0 = self._epoch
-            if nb != nb0 or batch != b0:
-                raise ValueError("set_epoch: a captured TrainStep keeps its order size")
-            o.copy_(order)
-            cursor.zero_()
-        self._host_cursor = 0
+        if self.walk is not None:
+            self.walk.reset(order, batch)
+            return
+        if self._cap is not None:
+            raise RuntimeError("set_epoch() must precede the first step of a non-epoch TrainStep")
+        self.walk = EpochWalk(self.pool, order, batch)
+        self._hist = torch.zeros((self.walk.n_batches, 3), dtype=torch.float32, pin_memory=True)
 
     def step_epoch(self):
         """The next batch of the epoch order (see set_epoch)."""
-        if self._epoch is None:
+        if self.walk is None:
             raise RuntimeError("step_epoch() needs set_epoch()")
-        row = self._host_cursor
-        self._host_cursor = (row + 1) % self._epoch[2]
+        row = self.walk.host_cursor
+        self.walk.host_cursor = (row + 1) % self.walk.n_batches
         if not self.capture:
             return tuple(self.eager_step(*self._gather()).tolist())
         self._ensure_epoch_graphs()
@@ -713,7 +515,7 @@ class TrainStep:
         return self._host_values(row)
 
     def _ensure_epoch_graphs(self):
-        if self._graphs is None:
+        if self._cap is None:
             y, t = self._gather()
             self._build_graphs(y, t, idx=torch.zeros(1, dtype=torch.int64, device=y.device))
 
@@ -724,10 +526,11 @@ class TrainStep:
         checks after epoch 10) a loss > 1e5 or NaN halts the epoch on the device right after that step's
         update and TrainingDivergedError is raised here, with the model, optimizer, RNG offset and cursor
         as the reference leaves them when it raises (only .grad holds the discarded next batch's gradient)."""
-        if self._epoch is None:
+        walk = self.walk
+        if walk is None:
             raise RuntimeError("run_epoch() needs set_epoch()")
-        nb = self._epoch[2]
-        start = self._host_cursor
+        nb = walk.n_batches
+        start = walk.host_cursor
         n = nb - start if n_steps is None else int(n_steps)
         if n < 0 or start + n > nb:
             raise ValueError(f"run_epoch: {n} steps from batch {start} exceed the epoch's {nb} batches")
@@ -742,6 +545,7 @@ class TrainStep:
                     raise TrainingDivergedError(f"Loss exploded to {v[0]} at batch {start + i}")
             return out
         self._ensure_epoch_graphs()
+        cap = self._cap
         self._guard.zero_()
         if check_divergence:
             # data parallel: judged on the all-reduced loss, the same on every rank. Hybrid: the reference judges
@@ -749,75 +553,66 @@ class TrainStep:
             # judged by bcnf_hybrid_finalize (world 1) / bcnf_guard_check_global (world > 1)
             self._guard[GUARD_CHECK if (self.world == 1 and not self.hybrid) else GUARD_CHECK_GLOBAL] = 1
         i = 0
-        if self.world == 1 and self.epoch_unroll > 1:
-            for k in self._unroll_sizes():
-                if n - i < k:
-                    continue
-                g, _, grads = self._multi_graph(k)
-                while n - i >= k:
+        if self.world == 1:
+            sched = graph_schedule(n, self.epoch_unroll, 2)
+            for k in dict.fromkeys(sched):              # each size's graph, as often as it fits, largest first
+                g, grads = self._multi_graph(k)
+                for _ in range(sched.count(k)):
                     g.replay()
-                    i += k
                 self._bind(grads)
-                self._rebind = True
-        if self.world > 1 and self._g21 is not None and n >= 2:
-            g1, g2, _ = self._graphs          # g1, then (all-reduce, g21) per later step, then the last update
-            g1.replay()
+                cap.rebind = True
+            i = sum(sched)
+        if self.world > 1 and cap.g21 is not None and n >= 2:
+            cap.g1.replay()                   # g1, then (all-reduce, g21) per later step, then the last update
             for _ in range(n - 1):
-                self._reduce_bucket()
-                self._g21.replay()
-            self._reduce_bucket()
-            g2.replay()
+                self.bucket.reduce()
+                cap.g21.replay()
+            self.bucket.reduce()
+            cap.g2.replay()
             i = n
         while i < n:
             self._replay(hidden=i < n - 1)
             i += 1
         torch.cuda.current_stream().synchronize()
         vals = [tuple(r) for r in self._hist[start:start + n].tolist()]
-        self._host_cursor = (start + n) % nb
+        walk.host_cursor = (start + n) % nb
         if check_divergence and int(self._guard[GUARD_DIVERGED].item()):
             for i, v in enumerate(vals):
                 if v[0] > 1e5 or math.isnan(v[0]):
-                    self._host_cursor = (start + i + 1) % nb
+                    walk.host_cursor = (start + i + 1) % nb
                     self._guard.zero_()
                     raise TrainingDivergedError(f"Loss exploded to {v[0]} at batch {start + i}")
         return vals
 
-    # Steps per captured graph in run_epoch: a graph boundary costs ~9 us of idle GPU between two replays
-    # (measured, r01j), so run_epoch replays `epoch_unroll` device-driven steps (cursor, RNG offset, Adam step,
-    # history row all advance on the device) per launch and the remainder in graphs of epoch_unroll / 2, / 4, ...
-    # steps (20 steps: 8 + 8 + 4, three launches instead of six) and a last single step.
+    # Steps per captured graph in run_epoch: run_epoch replays `epoch_unroll` device-driven steps (cursor, RNG
+    # offset, Adam step, history row all advance on the device) per launch and the remainder in graphs of
+    # epoch_unroll / 2, / 4, ... steps (epoch.graph_schedule) and a last single step.
     epoch_unroll = 8
-
-    def _unroll_sizes(self):
-        k, out = self.epoch_unroll, []
-        while k > 1:
-            out.append(k)
-            k //= 2
-        return out
     # The captured step runs the batch gather inside the folded path's pack launch (one launch fewer).
     fuse_gather = True
     # Inside a multi-step graph only the last step's clip-after-step is observable (see _update).
     skip_hidden_clips = True
 
     def _multi_graph(self, k: int):
-        if k not in self._multi:
-            self._bind(self._single_grads)         # every multi-step graph is captured from the same .grad state
+        cap = self._cap
+        if k not in cap.multi:
+            self._bind(cap.single_grads)           # every multi-step graph is captured from the same .grad state
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 slots = self._fold_adam_slots()
                 for i in range(k):
                     hidden = i < k - 1 and self.skip_hidden_clips
-                    sy, st, spec = self._gather(defer=True)
+                    sy, st, spec = self._gather(cap.idx, defer=True)
                     if hidden and slots is not None and self.model._foldable_linear(sy, (st,)) is not None:
                         # Adam of this step runs inside its folded backward tail (bcnf_fold_backward_tail)
                         self._forward_backward(sy, st, spec, adam=lambda v: self._fold_adam(slots, v))
                         continue
                     vals = self._forward_backward(sy, st, spec)
                     self._update(vals, clip=not (hidden and self.opt.can_bookkeep()))
-            self._multi[k] = (g, k, [p.grad for p in self.params])
-            self._bind(self._single_grads)
-            self._rebind = False
-        return self._multi[k]
+            cap.multi[k] = (g, [p.grad for p in self.params])
+            self._bind(cap.single_grads)
+            cap.rebind = False
+        return cap.multi[k]
 
     # Hidden steps of a folded model update their parameters inside the backward tail (no Adam launch).
     fuse_adam = True
@@ -850,11 +645,8 @@ class TrainStep:
         return slots
 
     def _fold_adam(self, slots, vals):
-        if self._book is None:
-            self._book = torch.zeros(1, dtype=torch.int32, device=self.params[0].device)
-        cursor = (self._epoch[1], self._epoch[2]) if self._epoch is not None else None
         log = (vals, self._hist) if self._hist is not None else None
-        spec = self.opt.fold_adam_spec(slots, cursor=cursor, log=log, counter=self._book, guard=self._guard)
+        spec = self.opt.fold_adam_spec(slots, cursor=self._cursor(), log=log, counter=self._book, guard=self._guard)
         if spec is None:
             raise RuntimeError("bcnf_amd TrainStep: the optimizer does not match the fused-Adam slots")
         return spec
@@ -869,26 +661,23 @@ class TrainStep:
     def prepare_epoch(self, n_steps: int):
         """Capture, without running anything, every graph a later run_epoch(n_steps) replays (the step graphs and,
         at world 1, the multi-step graph), so no capture lands inside a timed region."""
-        if self._epoch is None or not self.capture or self._no_fused_loss():
+        if self.walk is None or not self.capture or self._no_fused_loss():
             return
         self._ensure_epoch_graphs()
-        if self.world == 1 and self.epoch_unroll > 1:
-            i = 0
-            for k in self._unroll_sizes():
-                if n_steps - i >= k:
-                    self._multi_graph(k)
-                    i += k * ((n_steps - i) // k)
+        if self.world == 1:
+            for k in dict.fromkeys(graph_schedule(n_steps, self.epoch_unroll, 2)):
+                self._multi_graph(k)
 
     def _replay(self, hidden: bool = False):
-        if self._rebind:
-            self._bind(self._single_grads)
-            self._rebind = False
-        g1, g2, vals = self._graphs
-        g1.replay()
-        if g2 is not None:
-            self._reduce_bucket()           # the one collective of the step, between the two graph segments
-            (self._g2_hidden if hidden and self._g2_hidden is not None else g2).replay()
-        return vals
+        cap = self._cap
+        if cap.rebind:
+            self._bind(cap.single_grads)
+            cap.rebind = False
+        cap.g1.replay()
+        if cap.g2 is not None:
+            self.bucket.reduce()            # the one collective of the step, between the two graph segments
+            (cap.g2_hidden if hidden and cap.g2_hidden is not None else cap.g2).replay()
+        return cap.vals
 
 
 __all__ = ["TrainStep", "FusedAdam", "clip_grad_norm_", "TrainingDivergedError"]

@@ -35,7 +35,7 @@ from typing import Any, Callable
 import torch
 
 from bcnf_amd.errors import TrainingDivergedError
-from bcnf_amd.validate import ONE_CONDITION
+from bcnf_amd.validate import ONE_CONDITION, require_one_condition
 
 DEFAULT_RANDOM_STATE = 2024_03_25
 
@@ -180,9 +180,7 @@ class Trainer:
                 torch.distributed.get_world_size() > 1:
             raise NotImplementedError("bcnf_amd Trainer: world size > 1 is not supported (drive TrainStep's "
                                       "data-parallel step directly)")
-        conditions = config.get("global", {}).get("conditions")
-        if conditions is not None and len(conditions) > 1:
-            raise NotImplementedError(ONE_CONDITION)
+        require_one_condition(config)
         self.data = self._generate() if data is None else tuple(data)
         if len(self.data) != 2:
             raise NotImplementedError(ONE_CONDITION)
@@ -222,9 +220,7 @@ class Trainer:
         `stop_reason` are in `self.meta_scheduler`."""
         from bcnf_amd.train import TrainStep
         from bcnf_amd.validate import ValidationPass
-        fns = getattr(model, "feature_network_stack", None)
-        if fns is not None and getattr(fns, "n_distinct_conditions", 1) > 1:
-            raise NotImplementedError(ONE_CONDITION)
+        require_one_condition(model)
         cfg = self.config
         tr = cfg["training"]
         opt_cfg = cfg["optimizer"]

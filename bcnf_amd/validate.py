@@ -12,7 +12,7 @@ The reference runs, per validation batch, an eval-mode forward, three losses, `z
             loss = (nll + mse * w) / (1 + w)
             val_loss += loss.item(); ...
 
-`ValidationPass.run()` gathers each batch from a device pool on a device cursor (bcnf_gather_batch), runs the same
+`ValidationPass.run()` gathers each batch from a device pool on a device cursor (bcnf_amd/epoch.py), runs the same
 forward on the fused kernels and ONE bcnf_validation_stats launch per batch, which writes the batch's row
 `[loss, nll, mse, mean(ldj), z_mean[D], z_std[D]]`, adds the triple into a 3-double epoch sum on the device and
 advances the cursor. The whole batches are replayed as captured multi-batch graphs (8, 4, 2, 1 batches per graph, as
@@ -29,8 +29,23 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from bcnf_amd.epoch import DevicePool, EpochWalk, graph_schedule
+
 ONE_CONDITION = ("bcnf_amd: the device training loop serves models with ONE condition tensor (TrainStep's "
                  "one-condition limit: its pool, gather and captured step take a single condition)")
+
+
+def require_one_condition(model_or_config):
+    """NotImplementedError for a model whose feature stack takes, or a run config (dict) that lists, more than one
+    condition."""
+    if isinstance(model_or_config, dict):
+        conditions = model_or_config.get("global", {}).get("conditions")
+        many = conditions is not None and len(conditions) > 1
+    else:
+        fns = getattr(model_or_config, "feature_network_stack", None)
+        many = fns is not None and getattr(fns, "n_distinct_conditions", 1) > 1
+    if many:
+        raise NotImplementedError(ONE_CONDITION)
 
 
 def validation_stats_host(z, ldj, pred=None, y=None, w: float = 0.0):
@@ -83,37 +98,33 @@ class ValidationPass:
     unroll = 8         # batches per captured graph, then 4, 2, 1 (TrainStep.epoch_unroll)
 
     def __init__(self, model, hybrid_weight: float = 0.0, capture: bool = True):
-        fns = getattr(model, "feature_network_stack", None)
-        if fns is not None and getattr(fns, "n_distinct_conditions", 1) > 1:
-            raise NotImplementedError(ONE_CONDITION)
+        require_one_condition(model)
         self.model = model
         self.hybrid_weight = float(hybrid_weight)
         if self.hybrid_weight > 0.0 and not getattr(model, "hybrid", False):
             raise ValueError("bcnf_amd ValidationPass: hybrid_weight > 0 needs a model built with hybrid=True")
         self.layerwise = getattr(model, "_path", "fused") == "layerwise"
         self.capture = bool(capture) and not self.layerwise
-        self._pool = None
+        self.pool = None
         self._graphs = {}
         self.rows = None
 
     # ------------------------------------------------------------------ pool
     def set_pool(self, y_pool, cond_pool, batch: int):
-        for t in (y_pool, cond_pool):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise ValueError("ValidationPass.set_pool: contiguous fp32 device tensors required")
-        n, batch = int(y_pool.shape[0]), int(batch)
+        pool = DevicePool(y_pool, cond_pool, who="ValidationPass.set_pool")
+        n, batch = pool.n, int(batch)
         if n < 1 or cond_pool.shape[0] != n or batch < 1:
             raise ValueError("ValidationPass.set_pool: y_pool and cond_pool need the same, non-zero, number of rows "
                              "and batch >= 1")
-        dev = y_pool.device
-        self._pool = (y_pool, cond_pool)
+        dev = pool.device
+        self.pool = pool
         self.batch = batch
         self.n_whole = n // batch
         self.tail = n - self.n_whole * batch
         self.n_batches = self.n_whole + (1 if self.tail else 0)
         D = y_pool.shape[1]
-        self._order = torch.arange(max(self.n_whole * batch, 1), dtype=torch.int64, device=dev)
-        self._cursor = torch.zeros(1, dtype=torch.int64, device=dev)
+        # the whole batches, in the pool's own order; None when the pool is smaller than one batch
+        self.walk = EpochWalk(pool, torch.arange(self.n_whole * batch), batch) if self.n_whole else None
         self.rows = torch.zeros((self.n_batches, 4 + 2 * D), dtype=torch.float32, device=dev)
         self._sum = torch.zeros(3, dtype=torch.float64, device=dev)
         self._host_sum = torch.zeros(3, dtype=torch.float64).pin_memory()
@@ -139,14 +150,8 @@ class ValidationPass:
 
     def _whole_batch(self):
         """The cursor's batch: gather, forward, statistics into rows[cursor]; the stats launch advances the cursor."""
-        from bcnf_amd import _native as N
-        py, pc = self._pool
-        n = self.batch
-        y = torch.empty((n,) + tuple(py.shape[1:]), dtype=py.dtype, device=py.device)
-        c = torch.empty((n,) + tuple(pc.shape[1:]), dtype=pc.dtype, device=pc.device)
-        N.call("bcnf_gather_batch", self._order, self._cursor, n, py, py[0].numel(), y, pc, pc[0].numel(), c,
-               N.stream_handle(py.device))
-        self._stats(y, c, self.rows, self._cursor)
+        y, c = self.walk.gather()
+        self._stats(y, c, self.rows, self.walk.cursor)
 
     def _graph(self, k: int):
         if k not in self._graphs:
@@ -157,16 +162,9 @@ class ValidationPass:
             self._graphs[k] = g
         return self._graphs[k]
 
-    def _sizes(self):
-        k, out = self.unroll, []
-        while k >= 1:
-            out.append(k)
-            k //= 2
-        return out
-
     # ------------------------------------------------------------------ the epoch
     def run(self):
-        if self._pool is None:
+        if self.pool is None:
             raise RuntimeError("ValidationPass.run() needs set_pool()")
         m = self.model
         was_training = m.training
@@ -174,8 +172,9 @@ class ValidationPass:
         try:
             with torch.no_grad():
                 self._sum.zero_()
-                self._cursor.zero_()
                 n = self.n_whole
+                if n:
+                    self.walk.rewind()
                 if n and self.capture and not self._warm:
                     # allocations and kernel attributes settle outside any capture; the warm-up batches are whole
                     # batches of this epoch (the cursor walks on), so nothing is run twice
@@ -184,22 +183,17 @@ class ValidationPass:
                     with torch.cuda.stream(s):
                         self._whole_batch()
                         self._sum.zero_()
-                        self._cursor.zero_()
+                        self.walk.rewind()
                     torch.cuda.current_stream().wait_stream(s)
                     self._warm = True
-                i = 0
-                if self.capture:
-                    for k in self._sizes():
-                        while n - i >= k:
-                            self._graph(k).replay()
-                            i += k
-                while i < n:
+                sched = graph_schedule(n, self.unroll, 1) if self.capture else []
+                for k in sched:
+                    self._graph(k).replay()
+                for _ in range(n - sum(sched)):
                     self._whole_batch()
-                    i += 1
                 if self.tail:
-                    py, pc = self._pool
                     lo = n * self.batch
-                    self._stats(py[lo:], pc[lo:], self.rows[n], None)
+                    self._stats(self.pool.y[lo:], self.pool.cond[lo:], self.rows[n], None)
                 self._host_sum.copy_(self._sum, non_blocking=True)
                 self._host_row.copy_(self.rows[self.n_batches - 1], non_blocking=True)
                 torch.cuda.current_stream().synchronize()
@@ -217,4 +211,4 @@ class ValidationPass:
         return self._host_row.clone()
 
 
-__all__ = ["ValidationPass", "validation_stats", "validation_stats_host"]
+__all__ = ["ValidationPass", "require_one_condition", "validation_stats", "validation_stats_host"]

@@ -39,7 +39,7 @@ def _worker(rank, world, port, q):
         # gradients: rank r holds (r + 1) * base  ->  mean = base * (world + 1) / 2
         for i, p in enumerate(step.params):
             p.grad = torch.full_like(p, float(rank + 1)) * (i + 1)
-        step._allreduce()
+        step.bucket.allreduce()
         grads = [p.grad.detach().numpy().copy() for p in step.params]
         q.put((rank, sd, grads))               # numpy: no shared-memory handles outliving the worker
     except Exception:
@@ -82,8 +82,9 @@ def test_broadcast_and_allreduce_world2():
 
 def _overlap_worker(rank, world, port, q):
     """The overlapped exchange of the wide family (TrainStep.overlap_ranges): slices of the bucket all-reduced
-    asynchronously while the backward runs (WideStack.on_range -> _reduce_range), then the rest of the bucket and a
-    join (_reduce_bucket). Here the backward's writes are simulated on CPU: every gradient is a view of the bucket."""
+    asynchronously while the backward runs (WideStack.on_range -> GradBucket.reduce_range), then the rest of the bucket
+    and a join (GradBucket.reduce). Here the backward's writes are simulated on CPU: every gradient is a view of the
+    bucket."""
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -96,31 +97,31 @@ def _overlap_worker(rank, world, port, q):
         step = TrainStep(m, capture=False)
         for p in step.params:
             p.grad = torch.zeros_like(p)
-        step._allreduce()                                    # allocates the bucket; .grad become its views
-        n = step._bucket.numel()
+        step.bucket.allreduce()                              # allocates the bucket; .grad become its views
+        n = step.bucket.buf.numel()
         vals = torch.tensor([1.0 + rank, 2.0, 3.0])
         for i, p in enumerate(step.params):                  # rank r holds (r + 1) * (i + 1) * ramp
             p.grad.copy_(torch.linspace(0, 1, p.numel()).view_as(p) * float((rank + 1) * (i + 1)))
         # two "finished ranges" handed over out of order, one of them ending inside a parameter tensor
-        step._reduce_range(n // 2, n - 50)
-        step._reduce_range(7, n // 3)
-        assert len(step._works) == 2
-        out = step._allreduce(vals)
-        assert not step._works and not step._reduced
+        step.bucket.reduce_range(n // 2, n - 50)
+        step.bucket.reduce_range(7, n // 3)
+        assert len(step.bucket.works) == 2
+        out = step.bucket.allreduce(vals)
+        assert not step.bucket.works and not step.bucket.reduced
         res = [p.grad.detach().numpy().copy() for p in step.params]
-        # a step that raised after handing a slice over: the next step joins and forgets it first (_drain_slices)
-        step._reduce_range(0, 10)
-        step._drain_slices()
-        assert not step._works and not step._reduced
+        # a step that raised after handing a slice over: the next step joins and forgets it first (drain_slices)
+        step.bucket.reduce_range(0, 10)
+        step.bucket.drain_slices()
+        assert not step.bucket.works and not step.bucket.reduced
         # the stack hooks live only around a step's own backward, also when it raises
-        step._hooks = {"on_range": step._reduce_range, "range_blocks": [(0, 1)]}
+        step.bucket.hooks = {"on_range": step.bucket.reduce_range, "range_blocks": [(0, 1)]}
         with pytest.raises(ZeroDivisionError):
-            with step._stack_hooks():
+            with step.bucket.stack_hooks(m.fused):
                 assert m.fused.on_range is not None and m.fused.range_blocks == [(0, 1)]
                 1 / 0
         assert m.fused.on_range is None and m.fused.range_blocks is None
         q.put((rank, res, out.detach().numpy().copy(),
-               step._packed_inplace))
+               step.bucket.packed_inplace))
     except Exception:
         q.put((rank, traceback.format_exc(), None, None))
     finally:

@@ -68,7 +68,7 @@ def _worker(rank, world, port, cfg, q, mode="step"):
             except TrainingDivergedError as e:
                 raised = str(e)
             q.put((rank, ([p.detach().cpu().numpy() for p in m.parameters()],
-                          (raised, step._host_cursor, int(step._epoch[1].item())))))
+                          (raised, step.walk.host_cursor, int(step.walk.cursor.item())))))
             return
         if mode == "epoch":     # bench.py's N > 1 path: device pool, epoch order, run_epoch (gather in the graph)
             step.set_pool(y[rank * n:(rank + 1) * n].cuda(), t[rank * n:(rank + 1) * n].cuda())
@@ -83,7 +83,7 @@ def _worker(rank, world, port, cfg, q, mode="step"):
         else:
             for _ in range(STEPS):
                 step.step(y[rank * n:(rank + 1) * n].cuda(), t[rank * n:(rank + 1) * n].cuda())
-        q.put((rank, ([p.detach().cpu().numpy() for p in m.parameters()], step._packed_inplace)))
+        q.put((rank, ([p.detach().cpu().numpy() for p in m.parameters()], step.bucket.packed_inplace)))
     except Exception:
         q.put((rank, traceback.format_exc()))
     finally:

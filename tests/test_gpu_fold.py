@@ -171,12 +171,12 @@ def test_trainstep_pads_fold_pool(g1):
     st = TrainStep(m, lr=2e-4, capture=False)
     gen = torch.Generator().manual_seed(2)
     st.set_pool(torch.randn(64, 19, generator=gen).to(DEV), torch.randn(64, 30, 3, generator=gen).to(DEV))
-    assert st._pool[1].shape == (64, 92) and st._cond_shape == ((30, 3), 90)
-    assert torch.count_nonzero(st._pool[1][:, 90:]) == 0
+    assert st.pool.cond.shape == (64, 92) and st.pool.cond_shape == ((30, 3), 90)
+    assert torch.count_nonzero(st.pool.cond[:, 90:]) == 0
     m.fold_features = False
     st2 = TrainStep(m, lr=2e-4, capture=False)
     st2.set_pool(torch.randn(64, 19).to(DEV), torch.randn(64, 30, 3).to(DEV))
-    assert st2._cond_shape is None and st2._pool[1].shape == (64, 30, 3)
+    assert st2.pool.cond_shape is None and st2.pool.cond.shape == (64, 30, 3)
 
 
 @pytest.mark.parametrize("raw", [False, True])

@@ -276,13 +276,13 @@ def test_hybrid_run_epoch_equals_per_step_loop(g15, unroll):
         st.set_epoch(order, 48)
         if batched:
             st.prepare_epoch(15)
-            assert len(st._multi) > 0                        # the multi-step graphs exist: hybrid takes the epoch path
+            assert len(st._cap.multi) > 0                    # the multi-step graphs exist: hybrid takes the epoch path
             vals = st.run_epoch(1) + st.run_epoch()
         else:
             vals = [st.step_epoch() for _ in range(16)]
         state = [v.clone() for s in st.opt.state.values() for v in s.values()]
         res.append((vals, [p.detach().clone() for p in m.parameters()], state, m.fused.rng_state().clone(),
-                    st._epoch[1].item()))
+                    st.walk.cursor.item()))
     (v0, p0, s0, r0, c0), (v1, p1, s1, r1, c1) = res
     assert v0 == v1 and len(v1) == 16
     assert all(v[2] > 0.0 and abs(v[0] - 0.5 * (v[1] + v[2])) <= 1e-5 * abs(v[0]) for v in v1)
@@ -314,13 +314,13 @@ def test_guard_judges_the_combined_loss(g15):
         if mode == "epoch":
             with pytest.raises(TrainingDivergedError, match="at batch 0"):
                 st.run_epoch(check_divergence=True)
-            assert st._host_cursor == 1
+            assert st.walk.host_cursor == 1
         else:
             loss, nll, mse = st.step_epoch()
             assert loss > 1e5 and nll < 1e3 and mse > 1e7, (loss, nll, mse)
         state = [v.clone() for s in st.opt.state.values() for v in s.values()]
         res.append(([p.detach().clone() for p in m.parameters()], state, m.fused.rng_state().clone(),
-                    st._epoch[1].item()))
+                    st.walk.cursor.item()))
     (p0, s0, r0, c0), (p1, s1, r1, c1) = res
     assert c0 == c1 == 1 and torch.equal(r0, r1) and int(r1[1]) == 1
     for a, b in zip(p0 + s0, p1 + s1):

@@ -246,7 +246,7 @@ def test_run_epoch_equals_per_step_loop(g1, unroll, batch):
             vals = [st.step_epoch() for _ in range(nb)]
         state = [v.clone() for s in st.opt.state.values() for v in s.values()]
         res.append((vals, [p.detach().clone() for p in m.parameters()], state,
-                    m.fused.rng_state().clone(), st._epoch[1].item(), [p.grad.clone() for p in st.params]))
+                    m.fused.rng_state().clone(), st.walk.cursor.item(), [p.grad.clone() for p in st.params]))
     (v0, p0, s0, r0, c0, g0), (v1, p1, s1, r1, c1, gr1) = res
     assert v0 == v1 and len(v1) == nb
     assert c0 == c1 == 0 and torch.equal(r0, r1)
@@ -281,10 +281,10 @@ def test_run_epoch_divergence_halts_like_the_trainer(g1):
             # eager_epoch: the per-step host check raises right after batch 2's update, before batch 3 runs
             with pytest.raises(TrainingDivergedError, match="at batch 2"):
                 st.run_epoch(check_divergence=True)
-            assert st._host_cursor == 3
+            assert st.walk.host_cursor == 3
         state = [v.clone() for s in st.opt.state.values() for v in s.values()]
         res.append(([p.detach().clone() for p in m.parameters()], state, m.fused.rng_state().clone(),
-                    st._epoch[1].item()))
+                    st.walk.cursor.item()))
     (p0, s0, r0, c0) = res[0]
     for (p1, s1, r1, c1) in res[1:]:
         assert c0 == c1 == 3 and torch.equal(r0, r1)
@@ -337,7 +337,7 @@ def test_epoch_with_ragged_remainder_equals_eager_loop(g1):
             vals = st.run_epoch()
             vals += [st.step_indexed(rem1), st.step_indexed(rem7)]     # rem7 from the host: checked there
             vals += st.run_epoch()
-            cursor = st._epoch[1].item()
+            cursor = st.walk.cursor.item()
         else:
             vals = [st.step_indexed(b) for b in batches + [rem1, rem7] + batches]
             cursor = 0

@@ -111,7 +111,7 @@ def test_set_lr_reaches_the_captured_step(g21):
         if epoch == 1:
             steps[0].set_lr(5e-3)
             steps[1].set_lr(5e-3)
-            assert steps[1]._graphs is None and steps[1]._multi == {}
+            assert steps[1]._cap is None
             steps[2].opt.param_groups[0]["lr"] = 5e-3
     assert logged[0] == logged[1]
     for (n, pa), (_, pb), (_, pc) in zip(*(m.named_parameters() for m in models)):

@@ -38,4 +38,4 @@ step = TrainStep(model, lr=2e-4, capture=True)
 step.set_pool(data.y, data.traj)
 step.set_epoch(torch.cat([data.next_indices() for _ in range(4)]), 2048)
 step.run_epoch(2)
-print("calls", calls, "cond_shape", step._cond_shape)
+print("calls", calls, "cond_shape", step.pool.cond_shape)
