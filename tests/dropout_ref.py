@@ -107,7 +107,40 @@ SMALL_TRAIN_SHAPES = {
     "d7_h12_9": dict(size=7, nested_sizes=[12, 9], n_blocks=3, n_conditions=5, dropout=0.1, act_norm=False),
     "d32_nh1": dict(size=32, nested_sizes=[16], n_blocks=2, n_conditions=120, dropout=0.25, act_norm=True),
     "d2_h4x8": dict(size=2, nested_sizes=[4] * 8, n_blocks=5, n_conditions=3, dropout=0.3, act_norm=True),
+    # The template arms NH = 3 .. 6 and the shape edges no other case reaches (tests/small_arms.py names the arm each
+    # one takes; tests/test_small_arms_cpu.py holds the lists to them). Each of these runs at a weight gain
+    # (SMALL_TRAIN_GAIN), so that no gated tensor sits below its gate's absolute floor.
+    # NH = 4 (ActRec 2 + 3); 12 / 12, the last PERM layout; C = 17: Cp = 32, rows not 16-byte aligned (non-VEC)
+    "nh4_d24_c17": dict(size=24, nested_sizes=[16] * 4, n_blocks=3, n_conditions=17, dropout=0.2, act_norm=True),
+    # NH = 5 (3 + 1; the second dropout float4 opens); 13 / 12, the first non-PERM layout; uneven widths; C = KC
+    "nh5_d25_c128": dict(size=25, nested_sizes=[16, 7, 16, 3, 11], n_blocks=4, n_conditions=128, dropout=0.3,
+                         act_norm=True),
+    # NH = 6 (3 + 3; BwdJobs' exact fill); 10 / 10 without the 10 / 9 broadcast form; C = KC + 1; NKp = 128
+    "nh6_d20_c129": dict(size=20, nested_sizes=[16] * 6, n_blocks=5, n_conditions=129, dropout=0.25, act_norm=True),
+    # Da = 2, Db = 1; C = 1; no ActNorm
+    "nh6_d3_c1": dict(size=3, nested_sizes=[5] * 6, n_blocks=2, n_conditions=1, dropout=0.1, act_norm=False),
+    # 16 / 15; the widest C, in training
+    "nh4_d31_c208": dict(size=31, nested_sizes=[16] * 4, n_blocks=2, n_conditions=208, dropout=0.4, act_norm=True),
+    # NH = 3 in training (no other oracle-gated training case has it), on the 10 / 9 broadcast form
+    "nh3_d19_c80": dict(size=19, nested_sizes=[16] * 3, n_blocks=4, n_conditions=80, dropout=0.2, act_norm=True),
+    # nh8_p50 and d2_h4x8 again, at inputs their gates can see
+    "nh8_p50_g2": dict(size=19, nested_sizes=[16] * 8, n_blocks=3, n_conditions=80, dropout=0.5, act_norm=True),
+    "d2_h4x8_g3": dict(size=2, nested_sizes=[4] * 8, n_blocks=5, n_conditions=3, dropout=0.3, act_norm=True),
+    # behind ConcatenateCondition(X) + FullyConnected [X, C] (SMALL_TRAIN_FOLD_X): the pack-free folded forward at
+    # layouts other than FC_small's (fold_nh8_d22: every limit of its table at once), and the two-launch form at NH = 4
+    "fold_nh6_d19": dict(size=19, nested_sizes=[16] * 6, n_blocks=3, n_conditions=80, dropout=0.3, act_norm=True),
+    "fold_nh8_d22": dict(size=22, nested_sizes=[16] * 8, n_blocks=2, n_conditions=128, dropout=0.2, act_norm=True),
+    "fold_nh5_d18": dict(size=18, nested_sizes=[16] * 5, n_blocks=3, n_conditions=13, dropout=0.3, act_norm=True),
+    "fold_nh4_d24": dict(size=24, nested_sizes=[16] * 4, n_blocks=3, n_conditions=17, dropout=0.2, act_norm=True),
 }
+# apply_gain's factor per shape (absent: the weights stay as drawn)
+SMALL_TRAIN_GAIN = {"nh4_d24_c17": 2.0, "nh5_d25_c128": 2.0, "nh6_d20_c129": 2.0, "nh6_d3_c1": 2.5,
+                    "nh4_d31_c208": 2.0, "nh3_d19_c80": 2.0, "nh8_p50_g2": 2.0, "d2_h4x8_g3": 3.0,
+                    "fold_nh6_d19": 2.0, "fold_nh8_d22": 2.0, "fold_nh5_d18": 2.0, "fold_nh4_d24": 2.0}
+# in_features X of the single feature Linear [X, C] of the folded shapes (the input is (X / 3, 3) per sample), and
+# whether the pack-free forward's table applies to the layout (fold_nh4_d24: D^2 = 576 > 512 Q slots)
+SMALL_TRAIN_FOLD_X = {"fold_nh6_d19": 90, "fold_nh8_d22": 96, "fold_nh5_d18": 21, "fold_nh4_d24": 21}
+SMALL_TRAIN_RAW = {"fold_nh6_d19": True, "fold_nh8_d22": True, "fold_nh5_d18": True, "fold_nh4_d24": False}
 
 
 def shape_config(shape):
@@ -116,3 +149,28 @@ def shape_config(shape):
             "model": {"kwargs": dict(shape)},
             "feature_networks": [{"type": "ConcatenateCondition",
                                   "kwargs": {"input_size": None, "output_size": shape["n_conditions"]}}]}
+
+
+def fold_config(shape, X):
+    """from_config dict of the stack behind ConcatenateCondition(X) + FullyConnected [X, C] without feature dropout:
+    the single nn.Linear the folded training path takes in."""
+    cfg = shape_config(shape)
+    cfg["feature_networks"] = [{"type": "ConcatenateCondition", "kwargs": {"input_size": None, "output_size": X}},
+                               {"type": "FullyConnected", "kwargs": {"sizes": [X, shape["n_conditions"]],
+                                                                     "dropout": 0.0}}]
+    return cfg
+
+
+def apply_gain(target, gain):
+    """Multiply every 2-D `layers.*` weight (the coupling MLPs' Linears; never an orthonormal_matrix) of a model or
+    of a state dict (torch tensors or numpy arrays) by `gain`, in place; returns `target`. With default nn.Linear
+    init every GELU layer shrinks the signal, and at NH >= 6 the deepest gradients fall below the absolute floor of
+    their gate (conftest.close), where zeros pass; a gain of 2 .. 3 keeps them above it. Call it after the weights
+    are set and before the oracle's copy is taken, so model and oracle hold the same values."""
+    import torch
+    items = target.items() if isinstance(target, dict) else target.state_dict().items()
+    with torch.no_grad():
+        for k, v in items:
+            if k.startswith("layers.") and v.ndim == 2 and not k.endswith("orthonormal_matrix"):
+                v *= gain                        # state_dict() tensors share the parameters' storage
+    return target

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from conftest import FC_SMALL_CFG
-from dropout_ref import keep_bits
+from dropout_ref import SMALL_TRAIN_SHAPES, keep_bits, launch_sample, shape_config
 
 pytestmark = pytest.mark.gpu
 
@@ -57,20 +57,22 @@ def test_forward_dropout_masks_follow_the_32bit_rule(p, NH):
 
 
 def _small_train_cases():
-    from dropout_ref import SMALL_TRAIN_SHAPES, shape_config
     cases = {"fc_small": FC_SMALL_CFG}
     cases.update({k: shape_config(v) for k, v in SMALL_TRAIN_SHAPES.items()})
     return cases
 
 
-@pytest.mark.parametrize("case", ["fc_small", "nh8_p50", "d7_h12_9", "d32_nh1", "d2_h4x8"])
+MASK_CASES = ["fc_small"] + list(SMALL_TRAIN_SHAPES)
+
+
+@pytest.mark.parametrize("case", MASK_CASES)
 def test_forward_dropout_masks_at_the_parity_shapes(case):
     """The record check at the shapes tests/test_gpu_train_parity.py feeds to the oracle (hidden widths below 16,
-    NH = 1, 2, 7, 8), ragged B = 37: every unit of the real lanes of all 16 rows of each workgroup, the 11 rows past
-    the batch included (they replay sample B - 1, masks and all). Records: [k][workgroup][AR4][256 threads] float4,
-    AR4 = (2 NH + 3) / 4, floats (activation, derivative) of hidden layers 1..NH first (ActRec, bcnf_stack.hip)."""
+    every NH = 1 .. 8; a folded shape on its stack alone), ragged B = 37: every unit of the real lanes of all 16 rows
+    of each workgroup, the 11 rows past the batch included (they replay sample B - 1, masks and all). Records:
+    [k][workgroup][AR4][256 threads] float4, AR4 = (2 NH + 3) / 4, floats (activation, derivative) of hidden layers
+    1..NH first (ActRec, bcnf_stack.hip)."""
     from bcnf_amd import CondRealNVP_v2
-    from dropout_ref import launch_sample
     cfg = _small_train_cases()[case]
     kw = cfg["model"]["kwargs"]
     hidden, nb, p, C = kw["nested_sizes"], kw["n_blocks"], kw["dropout"], kw["n_conditions"]

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import FC_SMALL_CFG, close, golden_sd, load_golden
+from dropout_ref import SMALL_TRAIN_GAIN, SMALL_TRAIN_SHAPES, apply_gain
 from oracle import cnf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -149,7 +150,10 @@ def test_ballistic_trajectories_match_reference():
     assert close(inv.cpu(), d["inv"])[0]
 
 
-@pytest.mark.parametrize("B", [1, 15, 17, 33, 1000])
+RAGGED_B = [1, 15, 17, 33, 1000]
+
+
+@pytest.mark.parametrize("B", RAGGED_B)
 def test_ragged_batches_vs_oracle(model_g1, g1, B):
     sd = golden_sd(g1)
     gen = torch.Generator().manual_seed(B)
@@ -194,15 +198,21 @@ def test_empty_batch(model_g1):
     assert z.shape == (0, 19) and ldj.shape == (0,) and y.shape == (0, 19)
 
 
-@pytest.mark.parametrize("shape", [
-    dict(size=19, nested_sizes=[16] * 3, n_blocks=4, n_conditions=80, dropout=0.0, act_norm=True),
-    dict(size=7, nested_sizes=[12, 9], n_blocks=3, n_conditions=5, dropout=0.1, act_norm=False),
-    dict(size=32, nested_sizes=[16], n_blocks=2, n_conditions=120, dropout=0.0, act_norm=True),
-    dict(size=2, nested_sizes=[4] * 8, n_blocks=5, n_conditions=3, dropout=0.0, act_norm=True),
-])
-def test_other_shapes_vs_oracle(shape):
+# (shape, gain of dropout_ref.apply_gain): the last three are the NH = 4, 5, 6 training shapes of tests/dropout_ref.py
+# without dropout -- the eval forward (saving and not), eval gradient and eval inverse arms of those NH
+OTHER_SHAPES = [
+    (dict(size=19, nested_sizes=[16] * 3, n_blocks=4, n_conditions=80, dropout=0.0, act_norm=True), 1.0),
+    (dict(size=7, nested_sizes=[12, 9], n_blocks=3, n_conditions=5, dropout=0.1, act_norm=False), 1.0),
+    (dict(size=32, nested_sizes=[16], n_blocks=2, n_conditions=120, dropout=0.0, act_norm=True), 1.0),
+    (dict(size=2, nested_sizes=[4] * 8, n_blocks=5, n_conditions=3, dropout=0.0, act_norm=True), 1.0),
+] + [(dict(SMALL_TRAIN_SHAPES[k], dropout=0.0), SMALL_TRAIN_GAIN[k])
+     for k in ("nh4_d24_c17", "nh5_d25_c128", "nh6_d20_c129")]
+
+
+@pytest.mark.parametrize("shape,gain", OTHER_SHAPES, ids=[f"shape{i}" for i in range(4)] + ["nh4", "nh5", "nh6"])
+def test_other_shapes_vs_oracle(shape, gain):
     """Forward / inverse / eval grads for non-FC_small shapes (odd splits, no ActNorm, dropout stride 2/3,
-    padded C, 8 nested layers) against the oracle."""
+    padded C, 4, 5, 6 and 8 nested layers) against the oracle."""
     from bcnf_amd import CondRealNVP_v2, inn_nll_loss
     C = shape["n_conditions"]
     torch.manual_seed(7)
@@ -216,6 +226,8 @@ def test_other_shapes_vs_oracle(shape):
                 p.copy_(0.5 + torch.rand_like(p))
             elif n.endswith("bias") and n.count(".") == 2:
                 p.copy_(0.1 * torch.randn_like(p))
+    if gain != 1.0:
+        apply_gain(m, gain)
     sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
     spec = O.StackSpec(size=shape["size"], nested_sizes=shape["nested_sizes"], n_blocks=shape["n_blocks"],
                        n_conditions=C, dropout=shape["dropout"], act_norm=shape["act_norm"])
@@ -227,9 +239,21 @@ def test_other_shapes_vs_oracle(shape):
     z = m.forward(y.to(DEV), c.to(DEV), log_det_J=True)
     assert close(z.detach().cpu(), zr)[0]
     assert close(m.log_det_J.detach().cpu(), lr)[0]
+    assert z.requires_grad                                   # the saving forward; under no_grad the other one
     with torch.no_grad():
+        z0 = m.forward(y.to(DEV), c.to(DEV), log_det_J=True)
+        assert close(z0.cpu(), zr)[0]
+        assert close(m.log_det_J.cpu(), lr)[0]
         inv = m.inverse(zr.to(DEV), c.to(DEV))
     assert close(inv.cpu(), y, rtol=1e-4, floor=1e-4)[0]
+    if gain != 1.0:      # the NH = 4, 5, 6 shapes: the eval inverse of a latent draw against the fp64 oracle, at 1e-5
+        zlat = torch.randn(B, shape["size"])
+        sd64 = {k: v.double() for k, v in sd.items()}
+        inv_r = O.model_inverse(sd64, spec, zlat.double(), c.double())
+        with torch.no_grad():
+            inv = m.inverse(zlat.to(DEV), c.to(DEV))
+        ok, err = close(inv.cpu(), inv_r)
+        assert ok, err
     # eval-mode grads vs oracle autograd
     sdg = {k: v.clone().requires_grad_(not k.endswith("orthonormal_matrix")) for k, v in sd.items()}
     cg = c.clone().requires_grad_(True)

@@ -19,25 +19,40 @@ import pytest
 import torch
 
 from conftest import FC_SMALL_CFG, close, golden_sd, large_proxy_sd, load_golden
+from dropout_ref import apply_gain
 from oracle import cnf_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 NC = 7                                   # conditions behind cond_index
 
-# name -> (model kwargs, family). (a) PERM; (b) Da = Db = 16: non-PERM; (c) no ActNorm; (d) one block: no Q, no ActNorm
+# name -> (model kwargs, family). (a) PERM; (b) Da = Db = 16: non-PERM; (c) no ActNorm; (d) one block: no Q, no ActNorm;
+# (f) .. (l): the NH = 1, 4, 5, 6, 8 arms of k_inverse_mfma (tests/small_arms.py)
 CASES = {
     "a_perm": (dict(size=19, nested_sizes=[16] * 3, n_blocks=4, n_conditions=80, act_norm=True), "FusedStack"),
     "b_nonperm": (dict(size=32, nested_sizes=[16] * 2, n_blocks=3, n_conditions=24, act_norm=True), "FusedStack"),
     "c_no_actnorm": (dict(size=7, nested_sizes=[16] * 2, n_blocks=3, n_conditions=8, act_norm=False), "FusedStack"),
     "d_one_block": (dict(size=19, nested_sizes=[16] * 3, n_blocks=1, n_conditions=80, act_norm=True), "FusedStack"),
     "e_g1": (None, "FusedStack"),       # the reference's trained-shape weights, full depth (32 blocks, [16] * 7)
+    # NH = 4, 5, 6 (12 / 12 the last PERM layout, 13 / 12 the first non-PERM, 10 / 10), C = 17, KC, KC + 1; (g) has a
+    # hidden layer of width 1
+    "f_nh4_d24": (dict(size=24, nested_sizes=[16] * 4, n_blocks=3, n_conditions=17, act_norm=True), "FusedStack"),
+    "g_nh5_d25": (dict(size=25, nested_sizes=[16, 7, 16, 1, 11], n_blocks=4, n_conditions=128, act_norm=True),
+                  "FusedStack"),
+    "h_nh6_d20": (dict(size=20, nested_sizes=[16] * 6, n_blocks=5, n_conditions=129, act_norm=True), "FusedStack"),
+    # (i) NH = 1: the empty hidden-bias section of the matrix-core record (PMB); (j) NH = 8 at Da = 2, Db = 1 without
+    # ActNorm; (l) NH = 8 at D = 22: PMB = 3792 of the 4096 floats of a ring slot
+    "i_nh1_d23": (dict(size=23, nested_sizes=[16], n_blocks=3, n_conditions=1, act_norm=True), "FusedStack"),
+    "j_nh8_d3": (dict(size=3, nested_sizes=[5] * 8, n_blocks=2, n_conditions=16, act_norm=False), "FusedStack"),
+    "l_nh8_d22": (dict(size=22, nested_sizes=[16] * 8, n_blocks=2, n_conditions=128, act_norm=True), "FusedStack"),
     "w48": (dict(size=19, nested_sizes=[48] * 2, n_blocks=3, n_conditions=80, act_norm=True), "WideStack"),
     "w20_one_hidden": (dict(size=19, nested_sizes=[20], n_blocks=3, n_conditions=4, act_norm=True), "WideStack"),
     "w24_c13": (dict(size=19, nested_sizes=[24] * 2, n_blocks=2, n_conditions=13, act_norm=True), "WideStack"),
     "w526_fc_large": (dict(size=19, nested_sizes=[526] * 5, n_blocks=2, n_conditions=1360, act_norm=True),
                       "WideStack"),
 }
+# dropout_ref.apply_gain's factor on the coupling weights, after large_proxy_sd (absent: 1)
+GAIN = {"g_nh5_d25": 2.0, "h_nh6_d20": 2.0, "j_nh8_d3": 2.0, "l_nh8_d22": 2.0}
 ROWS = {name: ((64,) if name == "w526_fc_large" else (1, 37, 300)) for name in CASES}
 SMALL = [n for n, (_, fam) in CASES.items() if fam == "FusedStack"]
 WIDE = [n for n, (_, fam) in CASES.items() if fam == "WideStack"]
@@ -69,6 +84,8 @@ def _case(name):
                    {"type": "FullyConnected", "kwargs": {"sizes": [90, C], "dropout": 0.0}}]}
         m = CondRealNVP_v2.from_config(cfg)
         sd = {k: torch.from_numpy(v) for k, v in large_proxy_sd(m, 2024_03_25 + len(name)).items()}
+        if name in GAIN:
+            apply_gain(sd, GAIN[name])
         spec = O.StackSpec(size=kw["size"], nested_sizes=kw["nested_sizes"], n_blocks=kw["n_blocks"], n_conditions=C,
                            act_norm=kw["act_norm"], feature_sizes=[90, C])
         cond = torch.randn(NC, 30, 3, generator=torch.Generator().manual_seed(5))
@@ -172,7 +189,10 @@ def test_ldj_and_log_prob_match_the_fp64_oracle(name):
     _guard(name, ref)
 
 
-@pytest.mark.parametrize("name", ["a_perm", "b_nonperm", "e_g1", "w48", "w24_c13"])
+POSITION_CASES = ["a_perm", "b_nonperm", "e_g1", "w48", "w24_c13", "g_nh5_d25", "h_nh6_d20"]
+
+
+@pytest.mark.parametrize("name", POSITION_CASES)
 def test_rows_do_not_depend_on_their_position(name):
     m, sd, spec, cond, z, idx, ref = _case(name)
     h = _features(m, cond)

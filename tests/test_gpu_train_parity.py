@@ -26,7 +26,8 @@ import pytest
 import torch
 
 from conftest import FC_SMALL_CFG, close, golden_sd, load_golden
-from dropout_ref import SMALL_TRAIN_SHAPES, keep_callable, shape_config
+from dropout_ref import (SMALL_TRAIN_FOLD_X, SMALL_TRAIN_GAIN, SMALL_TRAIN_RAW, SMALL_TRAIN_SHAPES, apply_gain, fold_config,
+                         keep_callable, shape_config)
 from oracle import cnf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -82,8 +83,9 @@ def check(case, path, rows):
 
 
 # ------------------------------------------------------------------------------------------ oracle and GPU runs
-def oracle_run(case, keep, dtype=torch.float64):
-    """z, ldj, loss and every gradient of one training step on the oracle with the masks `keep`."""
+def oracle_run(case, keep, dtype=torch.float64, training=True):
+    """z, ldj, loss and every gradient of one training step on the oracle with the masks `keep` (training = False:
+    of one step in eval mode, no masks)."""
     spec = case.spec
     sdg = {k: v.to(dtype).clone().requires_grad_(not k.endswith("orthonormal_matrix")) for k, v in case.sd.items()}
     y = case.y.to(dtype).requires_grad_(True)
@@ -92,21 +94,24 @@ def oracle_run(case, keep, dtype=torch.float64):
         h.retain_grad()
     else:
         h = case.cond.to(dtype).requires_grad_(True)
-    z, ldj = O.model_forward(sdg, spec, y, h, training=True, keep=keep)
+    z, ldj = O.model_forward(sdg, spec, y, h, training=training, keep=keep)
     loss = O.inn_nll_loss(z, ldj)
     loss.backward()
     return dict(z=z.detach(), ldj=ldj.detach(), loss=loss.detach(), dy=y.grad, dh=h.grad,
                 grads={k: v.grad for k, v in sdg.items() if v.grad is not None})
 
 
-def gpu_run(case, path):
+def gpu_run(case, path, training=True):
     """One training step of `path` at the case's (seed, OFFSET): what the path exposes of z, ldj, loss, dL/dy, dL/dh
-    and the parameter gradients. Asserts the offset advanced by exactly one."""
+    and the parameter gradients. Asserts the offset advanced by exactly one (training = False: the same step of the
+    model in eval mode, which draws no masks and leaves the offset alone)."""
     from bcnf_amd import inn_nll_loss
     m, st = case.m, case.m.fused
     m.zero_grad(set_to_none=True)
+    m.train(training)
     st.rng_state()[1] = OFFSET
     y, cond = case.y.to(DEV), case.cond.to(DEV)
+    folded = path.startswith("folded")
     feats = []
 
     def grab(mod, args, out):
@@ -117,7 +122,7 @@ def gpu_run(case, path):
     hook = m.feature_network_stack.register_forward_hook(grab)
     out = {}
     try:
-        if path != "folded":
+        if not folded:
             y.requires_grad_(True)
             if not case.spec.feature_sizes:
                 cond.requires_grad_(True)
@@ -126,24 +131,30 @@ def gpu_run(case, path):
             loss = inn_nll_loss(z, m.log_det_J)
             out.update(z=z.detach().cpu(), ldj=m.log_det_J.detach().cpu())
         else:
-            m.fold_features = path == "folded"
+            m.fold_features = folded
+            if path == "folded_two":
+                st.use_raw_forward = False                # on the instance: pack + fold, then the forward
             try:
                 if not case.wide:
-                    assert (m._foldable_linear(y, (cond,)) is not None) == (path == "folded")
+                    assert (m._foldable_linear(y, (cond,)) is not None) == folded
+                if path in ("folded_raw", "folded_two"):
+                    assert (st.raw_table(case.spec.feature_sizes[0]) is not None) == (path == "folded_raw")
                 loss = m.nll_loss(y, cond)[0]
             finally:
                 del m.fold_features
+                st.__dict__.pop("use_raw_forward", None)
         loss.backward()
         if case.wide and path == "folded":
             with torch.no_grad():
                 assert m._wide_fold(y, (cond,)) is not None
     finally:
         hook.remove()
-    assert int(st.rng_state()[1].item()) == OFFSET + 1, "the RNG offset advances once per step"
+        m.train()
+    assert int(st.rng_state()[1].item()) == OFFSET + int(training), "the RNG offset advances once per step"
     out["loss"] = loss.detach().cpu()
     out["dy"] = y.grad.cpu() if y.grad is not None else None
     out["dh"] = feats[-1].grad.cpu() if feats and feats[-1].grad is not None else None
-    if path != "folded":
+    if not folded:
         assert out["dy"] is not None and out["dh"] is not None
     out["grads"] = {n: p.grad.detach().cpu().clone() for n, p in m.named_parameters() if p.grad is not None}
     m.zero_grad(set_to_none=True)
@@ -160,7 +171,14 @@ def _perturb(m):
 
 
 # ------------------------------------------------------------------------------------------ small family
-def _small_model(name):
+def small_seed(B):
+    """The Philox seed of every launch of a (shape, B) case (FusedStack.set_seed makes it a constant of the test)."""
+    return 0x5EED00000000 + B
+
+
+def small_weights(name):
+    """(model on the CPU, oracle spec, fp32 state dict) of a small-family case: no GPU. A shape with a gain
+    (SMALL_TRAIN_GAIN) has it applied after _perturb and before the oracle's copy is taken."""
     from bcnf_amd import CondRealNVP_v2
     if name == "fc_small":
         torch.manual_seed(0)
@@ -169,14 +187,16 @@ def _small_model(name):
         spec = O.FC_SMALL_SPEC
     else:
         shape = SMALL_TRAIN_SHAPES[name]
+        X = SMALL_TRAIN_FOLD_X.get(name)
         torch.manual_seed(7)
-        m = CondRealNVP_v2.from_config(shape_config(shape))
+        m = CondRealNVP_v2.from_config(shape_config(shape) if X is None else fold_config(shape, X))
         _perturb(m)
+        if name in SMALL_TRAIN_GAIN:
+            apply_gain(m, SMALL_TRAIN_GAIN[name])
         spec = O.StackSpec(size=shape["size"], nested_sizes=shape["nested_sizes"], n_blocks=shape["n_blocks"],
-                           n_conditions=shape["n_conditions"], dropout=shape["dropout"], act_norm=shape["act_norm"])
+                           n_conditions=shape["n_conditions"], dropout=shape["dropout"], act_norm=shape["act_norm"],
+                           feature_sizes=[] if X is None else [X, shape["n_conditions"]])
     sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    m.to(DEV).train()
-    assert type(m.fused).__name__ == "FusedStack"
     return m, spec, sd
 
 
@@ -186,31 +206,72 @@ def _small_keep(case, offset, rows, tag=0):
 
 
 @functools.lru_cache(maxsize=None)
-def small_case(name, B):
-    m, spec, sd = _small_model(name)
+def small_reference(name, B):
+    """A small-family case with its fp64 reference and no GPU: the model still on the CPU, the inputs, the seed the
+    launches will run at, and oracle_run with the masks of that seed at OFFSET. tests/test_small_arms_cpu.py checks
+    the conditions on the reference here; small_case moves the same object to the GPU."""
+    m, spec, sd = small_weights(name)
     g = torch.Generator().manual_seed(1000 + B)
     y = torch.randn(B, spec.size, generator=g)
-    cond = torch.randn(B, 30, 3, generator=g) if name == "fc_small" else torch.randn(B, spec.n_conditions, generator=g)
-    m.fused.set_seed(0x5EED00000000 + B)
-    seed = int(m.fused.rng_state()[0].item())             # read from the device state, as the launch does
-    case = types.SimpleNamespace(name=f"{name}-B{B}", m=m, spec=spec, sd=sd, y=y, cond=cond, seed=seed, wide=False)
+    if spec.feature_sizes:
+        cond = torch.randn(B, spec.feature_sizes[0] // 3, 3, generator=g)
+    else:
+        cond = torch.randn(B, spec.n_conditions, generator=g)
+    case = types.SimpleNamespace(name=f"{name}-B{B}", m=m, spec=spec, sd=sd, y=y, cond=cond, seed=small_seed(B),
+                                 wide=False)
     case.ref = oracle_run(case, _small_keep(case, OFFSET, B))
     return case
 
 
-SMALL = [("fc_small", 1), ("fc_small", 37), ("fc_small", 133), ("fc_small", 517)] + [(k, 37) for k in SMALL_TRAIN_SHAPES]
-SMALL_PATHS = [(n, B, p) for n, B in SMALL for p in ("unfused", "fused") + (("folded",) if n == "fc_small" else ())]
+@functools.lru_cache(maxsize=None)
+def small_case(name, B):
+    case = small_reference(name, B)
+    case.m.to(DEV).train()
+    assert type(case.m.fused).__name__ == "FusedStack"
+    case.m.fused.set_seed(case.seed)
+    assert int(case.m.fused.rng_state()[0].item()) == case.seed    # read from the device state, as the launch does
+    return case
+
+
+# (shape, B): FC_small, the shapes of before, and the new ones -- B = 37 for all, and B = 133 past KC rows of the W1
+# split-K for the two widest C
+SMALL = ([("fc_small", 1), ("fc_small", 37), ("fc_small", 133), ("fc_small", 517)]
+         + [(k, 37) for k in SMALL_TRAIN_SHAPES] + [("nh6_d20_c129", 133), ("nh4_d31_c208", 133)])
+NEW_SMALL = [(n, B) for n, B in SMALL if n in SMALL_TRAIN_GAIN]
+# folded_raw: the pack-free one-launch forward (bcnf_fold_train_forward); folded_two: pack + fold, then the forward
+# (use_raw_forward = False); folded: whichever of the two the library takes (FC_small: the first)
+SMALL_PATHS = [(n, B, p) for n, B in SMALL for p in
+               ("unfused", "fused") + (("folded",) if n == "fc_small" else ())
+               + (("folded_raw",) if SMALL_TRAIN_RAW.get(n) else ()) + (("folded_two",) if n in SMALL_TRAIN_RAW else ())]
 
 
 @pytest.mark.parametrize("name,B,path", SMALL_PATHS, ids=[f"{n}-B{B}-{p}" for n, B, p in SMALL_PATHS])
 def test_small_training_step_vs_fp64_oracle(name, B, path):
     """FC_small (g1 weights, p = 0.383) at B = 1, 37 (ragged: the 11 padded rows of the third workgroup draw masks
     too and must reach no gradient), 133 (past KC = 128 of the W1 condition split-K), 517 (past FIN_KC = 512 of the
-    folded tail), and the other small shapes at B = 37. unfused: m() + inn_nll_loss + autograd; fused: nll_loss with
+    folded tail), and the other small shapes at B = 37 (tests/dropout_ref.py: every NH = 1 .. 8, the split and C
+    edges; B = 133 too at C = 129 and C = 208). unfused: m() + inn_nll_loss + autograd; fused: nll_loss with
     fold_features = False; folded (FC_small): nll_loss with the feature Linear folded in, its gradients from
-    k_fold_splitk / k_fold_finish."""
+    k_fold_splitk / k_fold_finish. The four fold_* shapes run the folded step in both forms: folded_raw where the
+    pack-free forward's table applies (raw_table(X) is not None exactly there), folded_two with the two-launch form
+    forced -- each against the oracle, never against the other."""
     case = small_case(name, B)
+    if name in SMALL_TRAIN_RAW:
+        assert (case.m.fused.raw_table(case.spec.feature_sizes[0]) is not None) == SMALL_TRAIN_RAW[name]
     check(case, path, compare(gpu_run(case, path), case.ref))
+
+
+FOLD_EVAL = [("fc_small", 37)] + [(n, 37) for n, raw in SMALL_TRAIN_RAW.items() if raw]
+
+
+@pytest.mark.parametrize("name,B", FOLD_EVAL, ids=[f"{n}-B{B}" for n, B in FOLD_EVAL])
+def test_small_folded_eval_step_vs_fp64_oracle(name, B):
+    """k_forward<NH, false, true, true>: the pack-free folded step of a model in eval mode (no masks, the record
+    still saved for the backward), at every NH the table is run at. Same gates, the oracle in eval mode."""
+    case = small_case(name, B)
+    assert case.m.fused.raw_table(case.spec.feature_sizes[0]) is not None
+    ref = oracle_run(case, None, training=False)
+    check(case, "folded_raw-eval", compare(gpu_run(case, "folded_raw", training=False), ref))
 
 
 @pytest.mark.parametrize("name,B", SMALL, ids=[f"{n}-B{B}" for n, B in SMALL])
@@ -238,11 +299,17 @@ def test_small_nosave_training_forward_is_the_saving_forward(name, B):
     assert ok, err
 
 
-@pytest.mark.parametrize("name,B,tol", [("fc_small", 1, 1e-5), ("fc_small", 37, 1e-5), ("d7_h12_9", 1, 1e-4),
-                                        ("d7_h12_9", 37, 1e-4)])
+TRAIN_INVERSE = [("fc_small", 1, 1e-5), ("fc_small", 37, 1e-5), ("d7_h12_9", 1, 1e-4), ("d7_h12_9", 37, 1e-4),
+                 ("nh4_d24_c17", 1, 1e-5), ("nh4_d24_c17", 37, 1e-5), ("nh5_d25_c128", 1, 1e-5),
+                 ("nh5_d25_c128", 37, 1e-5), ("nh6_d20_c129", 1, 1e-5), ("nh6_d20_c129", 37, 1e-5),
+                 ("d32_nh1", 37, 1e-5), ("nh3_d19_c80", 37, 1e-5), ("nh8_p50_g2", 37, 1e-5)]
+
+
+@pytest.mark.parametrize("name,B,tol", TRAIN_INVERSE)
 def test_small_training_mode_inverse_vs_fp64_oracle(name, B, tol):
-    """model.train(); model.inverse(): k_inverse<NH, true>, masks drawn with tag 0x40000000. Gate as the eval inverse
-    test of the shape (test_ragged_batches_vs_oracle: 1e-5; test_other_shapes_vs_oracle: 1e-4)."""
+    """model.train(); model.inverse(): k_inverse<NH, true>, masks drawn with tag 0x40000000, at every NH = 1 .. 8. Gate
+    as the eval inverse test of the shape (test_ragged_batches_vs_oracle: 1e-5; test_other_shapes_vs_oracle: 1e-4);
+    1e-5 at the shapes with a gain and at d32_nh1."""
     case = small_case(name, 37)
     m, st, spec = case.m, case.m.fused, case.spec
     g = torch.Generator().manual_seed(B)
