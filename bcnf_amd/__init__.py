@@ -13,6 +13,8 @@ from bcnf_amd.data import VideoBatches
 from bcnf_amd.generate import generate_data, generate_data_device, sample_candidates_host
 from bcnf_amd.render import (camera, camera_basis, get_cams_position, record_trajectory, render_device, render_host,
                              standard_normals, visibility)
+from bcnf_amd.resimulation_stats import (impacts_device, impacts_host, resimulation_error_device,
+                                         resimulation_error_host, resimulation_summary)
 from bcnf_amd.sampling import posterior_mode
 from bcnf_amd.trainer import Trainer, TrainerParameterHistoryHandler
 from bcnf_amd.utils import ParameterIndexMapping, inn_nll_loss, load_config, log_prob_from_latent
@@ -28,4 +30,5 @@ __all__ = [
     "render_host", "standard_normals", "visibility", "VideoBatches",
     "generate_data", "generate_data_device", "sample_candidates_host",
     "Trainer", "TrainerParameterHistoryHandler", "ValidationPass",
+    "resimulation_error_device", "resimulation_error_host", "impacts_device", "impacts_host", "resimulation_summary",
 ]

@@ -50,8 +50,11 @@ EXPORTS = (
     "bcnf_conv_block_forward", "bcnf_conv_block_work_bytes", "bcnf_conv_block_backward",
     "bcnf_render_frames", "bcnf_render_frames_at", "bcnf_render_lit", "bcnf_sample_candidates",
     "bcnf_validation_stats",
+    "bcnf_resim_error_median", "bcnf_resim_impacts",
 )
 ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
+RESIM_ERROR_MAX_DRAWS = 16384     # include/bcnf_amd.h BCNF_RESIM_ERROR_MAX_DRAWS
+RESIM_HIST_MAX_EDGES = 192        # include/bcnf_amd.h BCNF_RESIM_HIST_MAX_EDGES
 MAX_TENSORS = 48
 
 
@@ -207,6 +210,8 @@ def _bind(lib):
         "bcnf_rank_count": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
         "bcnf_resimulate": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _i32, ctypes.c_double, _i32,
                                    ctypes.c_double, ctypes.c_double, _i32, _vp, _vp, _vp, _vp]),
+        "bcnf_resim_error_median": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp]),
+        "bcnf_resim_impacts": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
         "bcnf_wide_gemm_test": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
         "bcnf_wide_backward_plan": (_i32, [_pdesc, _i64, _i32, _i32, _i32, _i32, _i32, _pi64]),
         "bcnf_head_work_bytes": (_i32, [_i64, _i32, _i32, _pi64]),

@@ -9,11 +9,15 @@ i.e. the reference's CPU-generator z stream and chunking, so the ranks equal the
 z_stream = "device": draws are generated on the GPU (`bcnf_amd.sampling.draw`, seedable `generator`) in chunks of
 `chunk_draws` and counted as they are produced; the (M, N, D) tensor of all draws is never materialised.
 
+`CDF`, `brownian_confidence_interval` and `compute_CDF_residuals` (eval/calibration.py:7-17, 51-71) are the rest of
+the module: plain numpy on the (N, D) ranks, with the reference's signatures and results.
+
 Deviation: the reference moves the model to `device` (default 'cpu'); the HIP kernels need the GPU, so a CPU
 `device` keeps the model where it is (it must already be on a ROCm device).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from bcnf_amd import _native as N
@@ -64,4 +68,33 @@ def compute_y_hat_ranks(model, y: torch.Tensor, *conditions: torch.Tensor, M_sam
     return counts.to(torch.int64).to(output_device)
 
 
-__all__ = ["compute_y_hat_ranks", "rank_count_"]
+def CDF(sorted_arrray_indices, t: np.ndarray, M: int) -> np.ndarray:
+    """Empirical CDF of the ranks (eval/calibration.py:7-10): for ranks (N, D) and t in [0, 1], the (D, len(t)) share of
+    the N rows whose rank is <= t M."""
+    ranks = np.asarray(sorted_arrray_indices)
+    levels = np.asarray(t) * M
+    return np.sum(ranks[:, :, None] <= levels[None, None, :], axis=0) / ranks.shape[0]
+
+
+def brownian_confidence_interval(t: np.ndarray) -> np.ndarray:
+    """Standard deviation sqrt(t (1 - t)) of a Brownian bridge at t (eval/calibration.py:13-17); the 1 / sqrt(N) is
+    applied to the residuals by compute_CDF_residuals instead."""
+    t = np.asarray(t)
+    return np.sqrt(t * (1 - t))
+
+
+def compute_CDF_residuals(y_hat_all_sorted_ranks, M_samples: int, t_divisions: int = 100,
+                          sigma: float = 1) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(t, scaled residuals (D, t_divisions), confidence interval) of eval/calibration.py:51-71 for the (N, D) ranks
+    compute_y_hat_ranks returns (tensor on any device, or numpy): t = linspace(0, 1, t_divisions), residuals =
+    (CDF(ranks, t, M_samples) - t) sqrt(N) / sigma, interval = brownian_confidence_interval(t)."""
+    ranks = y_hat_all_sorted_ranks
+    if isinstance(ranks, torch.Tensor):
+        ranks = ranks.detach().cpu().numpy()
+    ranks = np.asarray(ranks)
+    t = np.linspace(0, 1, t_divisions)
+    scaled = (CDF(ranks, t, M_samples) - t) * np.sqrt(ranks.shape[0]) / sigma
+    return t, scaled, brownian_confidence_interval(t)
+
+
+__all__ = ["compute_y_hat_ranks", "rank_count_", "CDF", "brownian_confidence_interval", "compute_CDF_residuals"]

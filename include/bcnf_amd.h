@@ -38,6 +38,9 @@
  *   bcnf_rank_count      <- the rank count of compute_y_hat_ranks (eval/calibration.py:42-46)
  *   bcnf_resimulate      <- resimulate's per-draw physics_ODE_simulation map (simulation/resimulation.py:12-18,
  *                           49-56 -> simulation/physics.py:53-160)
+ *   bcnf_resim_error_median / bcnf_resim_impacts
+ *                        <- notebooks/resimulation.ipynb's reductions of the re-simulated positions: the nanmedian over
+ *                           the draws of the squared error, and the impacts (np.diff of z > 0) with their hist2d
  *   bcnf_render_frames   <- camera() per frame of record_trajectory, per camera of generate_data
  *                           (simulation/camera.py:30-150, simulation/sampling.py:366-368)
  *   bcnf_sample_candidates / bcnf_render_lit / bcnf_render_frames_at
@@ -635,6 +638,43 @@ int bcnf_resimulate(const void* y_hat, int32_t y_hat_f64, int64_t n_draws, int64
                     const int32_t* param_cols, const double* fixed, const double* tgrid, int32_t steps, double dt,
                     int32_t break_on_impact, double rtol, double atol, int32_t max_attempts, double* x,
                     int32_t* attempts, int32_t* status, void* stream);
+
+/* ---- Re-simulation statistics (notebooks/resimulation.ipynb: what the notebook reduces bcnf_resimulate's positions
+ * to). x is the (n_traj, n_draws, steps, 3) float64 output of bcnf_resimulate, device memory, steps >= 1; both entry
+ * points reduce over the draw axis, check their arguments before any device call and do nothing for
+ * n_traj * n_draws == 0.
+ *
+ * bcnf_resim_error_median: err[i * steps + s] =
+ * np.nanmedian(np.nanmean((x - observed[:, None])**2, axis=3), axis=1)[i][s], bit for bit. observed is (n_traj,
+ * steps, 3), float32 or (observed_f64) float64. Per draw j:
+ * e_k = (x[i][j][s][k] - (double)observed[i][s][k])^2, each operation rounded on its own (no FMA), the value is
+ * (the sum of the non-NaN e_k in the order k = 0, 1, 2) / their number, or NaN when all three are NaN. err is the
+ * median of the c non-NaN values: the middle one for odd c, (lo + hi) / 2 for even c, NaN for c = 0. The median is
+ * found by an exact sort of the values' bit patterns inside one workgroup's LDS, so the result is the same bits on
+ * every run. One deviation from numpy: for odd c and n_draws < 600 numpy's small-array path returns (v + v) / 2,
+ * which is inf for v > DBL_MAX / 2; this returns v.
+ * n_draws <= BCNF_RESIM_ERROR_MAX_DRAWS (a column of draws, padded to a power of two, is sorted in LDS: 16384 keys of
+ * 8 bytes = 128 KB of the 160 KB a gfx950 workgroup has); more returns BCNF_ERR_UNSUPPORTED and launches nothing.
+ *
+ * bcnf_resim_impacts: with above[s] = x[i][j][s][2] > 0 (false for NaN), a transition of draw (i, j) is a step s in
+ * [0, steps - 2] with above[s] && !above[s + 1], i.e. an index of np.diff((x[i, :, :, 2] > 0).astype(int)) == -1: the
+ * last step still above ground. step[i * n_draws + j] is the first transition or -1, position[(i * n_draws + j) * 3 + k]
+ * = x[i][j][step][k] or NaN, transitions[i * n_draws + j] their number (thrust can lift a ball again). With edges
+ * (n_edges float64 values, strictly increasing, device memory, used for both axes) and hist (n_traj, n_edges - 1,
+ * n_edges - 1) int32, hist[i] counts the (x, y) = x[i][j][s][0 .. 1] of EVERY transition of trajectory i as
+ * np.histogram2d(xs, ys, bins=edges) does: bin np.searchsorted(edges, v, 'right') - 1 per axis (first index: the x bin),
+ * a value equal to the last edge in the last bin, values outside the edges, NaN and +-inf dropped. hist is written
+ * whole (one workgroup owns hist[i], counted in LDS). edges and hist are both NULL or both given.
+ * 2 <= n_edges <= BCNF_RESIM_HIST_MAX_EDGES (the (n_edges - 1)^2 int32 counters and the edge table live in one
+ * workgroup's LDS: 147,460 bytes at 192 edges; 128 edges need 65,540); more returns BCNF_ERR_UNSUPPORTED and launches
+ * nothing. */
+#define BCNF_RESIM_ERROR_MAX_DRAWS 16384
+#define BCNF_RESIM_HIST_MAX_EDGES 192
+int bcnf_resim_error_median(const double* x, const void* observed, int32_t observed_f64, int64_t n_traj,
+                            int64_t n_draws, int32_t steps, double* err, void* stream);
+int bcnf_resim_impacts(const double* x, int64_t n_traj, int64_t n_draws, int32_t steps, const double* edges,
+                       int32_t n_edges, int32_t* step, double* position, int32_t* transitions, int32_t* hist,
+                       void* stream);
 
 /* ---- Camera (simulation/camera.py:74-150 camera(), looped by record_trajectory, camera.py:30-71, and over the two
  * cameras of a sample by generate_data, sampling.py:366-368) -----------------------------------------------------------
