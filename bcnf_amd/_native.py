@@ -15,7 +15,7 @@ import threading
 import torch  # noqa: F401  (must precede loading the HIP library)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("BCNF_AMD_LIB") or os.path.join(_HERE, "libbcnf_amd.so")   # override: A/B experiments
+LIB_PATH = os.environ.get("BCNF_AMD_LIB") or os.path.join(_HERE, "libbcnf_amd.so")   # another build of this tree
 
 MAX_HIDDEN = 8
 
@@ -39,7 +39,7 @@ EXPORTS = (
     "bcnf_wide_supported", "bcnf_wide_param_count", "bcnf_wide_packed_bytes", "bcnf_wide_workspace_bytes", "bcnf_wide_inverse_scratch_bytes",
     "bcnf_wide_pack", "bcnf_wide_forward", "bcnf_wide_nll_finalize", "bcnf_wide_backward", "bcnf_wide_inverse",
     "bcnf_wide_fold_prepare", "bcnf_wide_fold_forward", "bcnf_wide_fold_backward", "bcnf_wide_proj_rows",
-    "bcnf_wide_fold_backward_range", "bcnf_wide_fold_backward_phase", "bcnf_wide_block_offset",
+    "bcnf_wide_block_offset",
     "bcnf_wide_gemm_test", "bcnf_wide_backward_plan", "bcnf_rank_count", "bcnf_resimulate",
     "bcnf_guard_check_global", "bcnf_abi_version",
     "bcnf_head_work_bytes", "bcnf_head_mse_forward", "bcnf_head_mse_backward", "bcnf_hybrid_finalize",
@@ -52,7 +52,7 @@ EXPORTS = (
     "bcnf_validation_stats",
     "bcnf_resim_error_median", "bcnf_resim_impacts",
 )
-ABI_VERSION = 2          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts below)
+ABI_VERSION = 3          # include/bcnf_amd.h BCNF_AMD_ABI_VERSION (the struct layouts and signatures below)
 RESIM_ERROR_MAX_DRAWS = 16384     # include/bcnf_amd.h BCNF_RESIM_ERROR_MAX_DRAWS
 RESIM_HIST_MAX_EDGES = 192        # include/bcnf_amd.h BCNF_RESIM_HIST_MAX_EDGES
 MAX_TENSORS = 48
@@ -195,11 +195,7 @@ def _bind(lib):
         "bcnf_wide_fold_prepare": (_i32, [_pdesc, _vp, _vp, _i32, _vp, _vp]),
         "bcnf_wide_fold_forward": (_i32, [_pdesc, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
         "bcnf_wide_fold_backward": (_i32, [_pdesc, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
-                                           _vp, _vp]),
-        "bcnf_wide_fold_backward_range": (_i32, [_pdesc, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
-                                                 _vp, _vp, _i32, _i32, _vp]),
-        "bcnf_wide_fold_backward_phase": (_i32, [_pdesc, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
-                                                 _vp, _vp, _i32, _vp]),
+                                           _vp, _i32, _i32, _vp]),
         "bcnf_wide_block_offset": (_i32, [_pdesc, _i32, _pi64]),
         "bcnf_wide_proj_rows": (_i32, [_pdesc, _pi64]),
         "bcnf_wide_nll_finalize": (_i32, [_pdesc, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
@@ -244,10 +240,7 @@ def _bind(lib):
         "bcnf_status_string": (ctypes.c_char_p, [_i32]),
         "bcnf_abi_version": (_i32, []),
     }
-    override = "BCNF_AMD_LIB" in os.environ     # an explicit A/B build (tools/): it may predate newer entry points
     for name, (res, args) in sig.items():
-        if override and not hasattr(lib, name):
-            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -265,8 +258,7 @@ def lib():
                         "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).")
                 handle = ctypes.CDLL(LIB_PATH)
                 _bind(handle)
-                if (hasattr(handle, "bcnf_abi_version") or "BCNF_AMD_LIB" not in os.environ) and \
-                        handle.bcnf_abi_version() != ABI_VERSION:
+                if handle.bcnf_abi_version() != ABI_VERSION:
                     raise RuntimeError(f"bcnf_amd: {LIB_PATH} has ABI version {handle.bcnf_abi_version()}, the "
                                        f"bindings expect {ABI_VERSION}: rebuild the library")
                 _lib = handle

@@ -2563,9 +2563,8 @@ int wide_forward(const WideLayout& L, const float* prm, const float* pk, const f
 // The G region's split-K scratch plan of one wide_backward call (host arithmetic only; bcnf_wide_backward_plan
 // exposes it to the CPU tests and the ASan run, tools/asan_host.sh). The G region holds nv * NH slabs of B * HP
 // floats. The last range's dL/dx and [dWf | dbf] put their split-K partials at its END (`tail` floats), the parameter
-// gradients of the range use the range's own G slots from its head (`gsc_off`, `gsc_floats`), so phase 1 and phase 2
-// may run on two streams. A need larger than the whole region reserves nothing (that GEMM runs unsplit), and the
-// head region is clamped to what the tail leaves.
+// gradients of the range use the range's own G slots from its head (`gsc_off`, `gsc_floats`). A need larger than the
+// whole region reserves nothing (that GEMM runs unsplit), and the head region is clamped to what the tail leaves.
 struct GPlan {
   long long gfl_all, dx_need, dwfb_need, tail, gsc_off, gsc_floats;
 };
@@ -2586,19 +2585,14 @@ GPlan g_plan(const WideLayout& L, long long B, bool dx, bool dwfb, int Xp, int b
 // Real blocks [blo, bhi) of the backward: the chain iterations that complete them, then their parameter gradients
 // (canonical flat, every element written exactly once). The whole backward is [0, nb). A data-parallel caller may
 // split it into descending contiguous ranges, the first with bhi = nb, and reduce each range's gradient slice while
-// the next range runs (bcnf_wide_fold_backward_range); the range with blo = 0 also runs what needs every block (fold:
+// the next range runs (bcnf_wide_fold_backward); the range with blo = 0 also runs what needs every block (fold:
 // the feature-Linear gradients and dL/dx; else dL/dh). The chain iteration v finishes virtual block v (tail-B: dZ_0)
 // and starts v - 1 (head-B, then its hidden-layer chain), so a range runs v = (vhi == nv ? nv : vhi - 1) .. vlo.
 // Per-element results do not depend on the split: every GEMM keeps its K order, the split-K partials of the small
 // Linear gradients go to the finished range's G slots (dead once its chain has run).
-// phase (whole range only): bit 1 = what the caller's next layers wait for (the chain, then Gx, dL/dx, [dWf | dbf] /
-// dL/dh), bit 2 = the coupling parameter gradients. Bit 2 reads only the workspace, Gx and the operands and puts its
-// split-K partials at the head of the G region, bit 1's at its tail, so a caller may run bit 2 on a second stream
-// (after bit 1's chain in stream order) while its own backward continues on the first.
 int wide_backward(const WideLayout& L, const float* prm, const float* pk, const float* h, const float* zn,
                   const float* dz, const float* dldj, const float* dvals, int nll, long long B, float* ws, float* dy,
-                  float* dh, float* dprm, hipStream_t st, const WideFold* fold = nullptr, int blo = 0, int bhi = -1,
-                  int phase = 3) {
+                  float* dh, float* dprm, hipStream_t st, const WideFold* fold = nullptr, int blo = 0, int bhi = -1) {
   if (B == 0) return BCNF_OK;
   if (bhi < 0) bhi = L.nb;
   if (blo < 0 || bhi > L.nb || blo >= bhi) return BCNF_ERR_ARG;
@@ -2618,7 +2612,6 @@ int wide_backward(const WideLayout& L, const float* prm, const float* pk, const 
     *ld = L.HP;
     return w.dZ + ((long long)v * (L.NH - 1) + (l - 1)) * slab;
   };
-  if (phase & 1) {
   for (int v = vhi == L.nv ? L.nv : vhi - 1; v >= vlo; --v) {
     // link: tail-B(v) (v < nv), head-B(v-1)
     LinkBArgs a;
@@ -2682,8 +2675,6 @@ int wide_backward(const WideLayout& L, const float* prm, const float* pk, const 
     GemmArgs g = gemm_args(L.tiling, (int)B, L.C, L.nv * L.HP, w.dZ0, ld0, pk + L.pk_w0h, L.Cp, dh, L.C);
     WCHK((gemm<true, false, EPI_STORE>(g, 1, st)));
   }
-  }
-  if (!(phase & 2)) return BCNF_OK;
   int rc = BCNF_OK;
   const float* hp = fold ? nullptr : padded_h(L, h, B, w.Hp, st, &rc);
   WCHK(rc);
@@ -2943,37 +2934,7 @@ int bcnf_wide_fold_forward(const BcnfStackDesc* desc, const float* params, const
 int bcnf_wide_fold_backward(const BcnfStackDesc* desc, const float* params, const void* packed, const float* x1,
                             int32_t xp, const float* wfb, const float* wcb, const float* z, const float* dloss,
                             int64_t batch, void* workspace, float* gx_scratch, float* dparams, float* dwfb, float* dx,
-                            void* stream) {
-  WideLayout L;
-  WCHK(wide_layout(desc, &L));
-  if (batch < 1 || !params || !packed || !x1 || !wfb || !wcb || !z || !workspace || !gx_scratch || !dparams ||
-      xp < 4 || (xp & 3) || !aligned16(x1) || !aligned16(wfb) || !aligned16(wcb) || !aligned16(gx_scratch) ||
-      (dwfb && !aligned16(dwfb)) || (dx && !aligned16(dx)))
-    return BCNF_ERR_ARG;
-  WideFold f = {x1, wfb, wcb, gx_scratch, dwfb, dx, (int)xp};
-  return wide_backward(L, params, (const float*)packed, nullptr, z, nullptr, nullptr, dloss, 1, batch,
-                       (float*)workspace, nullptr, nullptr, dparams, (hipStream_t)stream, &f);
-}
-
-int bcnf_wide_fold_backward_phase(const BcnfStackDesc* desc, const float* params, const void* packed, const float* x1,
-                                  int32_t xp, const float* wfb, const float* wcb, const float* z, const float* dloss,
-                                  int64_t batch, void* workspace, float* gx_scratch, float* dparams, float* dwfb,
-                                  float* dx, int32_t phase, void* stream) {
-  WideLayout L;
-  WCHK(wide_layout(desc, &L));
-  if (batch < 1 || !params || !packed || !x1 || !wfb || !wcb || !z || !workspace || !gx_scratch || !dparams ||
-      xp < 4 || (xp & 3) || !aligned16(x1) || !aligned16(wfb) || !aligned16(wcb) || !aligned16(gx_scratch) ||
-      (dwfb && !aligned16(dwfb)) || (dx && !aligned16(dx)) || phase < 1 || phase > 3)
-    return BCNF_ERR_ARG;
-  WideFold f = {x1, wfb, wcb, gx_scratch, dwfb, dx, (int)xp};
-  return wide_backward(L, params, (const float*)packed, nullptr, z, nullptr, nullptr, dloss, 1, batch,
-                       (float*)workspace, nullptr, nullptr, dparams, (hipStream_t)stream, &f, 0, -1, phase);
-}
-
-int bcnf_wide_fold_backward_range(const BcnfStackDesc* desc, const float* params, const void* packed, const float* x1,
-                                  int32_t xp, const float* wfb, const float* wcb, const float* z, const float* dloss,
-                                  int64_t batch, void* workspace, float* gx_scratch, float* dparams, float* dwfb,
-                                  float* dx, int32_t block_lo, int32_t block_hi, void* stream) {
+                            int32_t block_lo, int32_t block_hi, void* stream) {
   WideLayout L;
   WCHK(wide_layout(desc, &L));
   if (batch < 1 || !params || !packed || !x1 || !wfb || !wcb || !z || !workspace || !gx_scratch || !dparams ||

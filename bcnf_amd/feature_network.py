@@ -24,7 +24,6 @@ Restated from the reference's behaviour (src/bcnf/models/feature_network.py); th
 from __future__ import annotations
 
 import math
-import os
 import weakref
 from typing import Any, Type
 
@@ -251,16 +250,11 @@ class LSTMFeatureNetwork(FeatureNetwork):
         self.pooling = pooling
         self.pool_dim = pool_dim
 
-    # The LSTM itself stays on PyTorch-ROCm (north star): MIOpen's fused RNN kernels by default; False runs torch's
-    # native per-step GEMM + pointwise kernels instead (BCNF_LSTM_MIOPEN=0; tools/gpu_r04.sh lstmab measures both).
-    use_miopen = os.environ.get("BCNF_LSTM_MIOPEN", "1") != "0"
-
     def lstm_out(self, x: torch.Tensor) -> torch.Tensor:
-        """The LSTM's output sequence (B, T, hidden * directions)."""
-        if self.use_miopen or not x.is_cuda:
-            return self.lstm(x)[0]
-        with torch.backends.cudnn.flags(enabled=False):
-            return self.lstm(x)[0]
+        """The LSTM's output sequence (B, T, hidden * directions). The LSTM itself stays on PyTorch-ROCm (north star):
+        MIOpen's fused RNN kernels, measured against torch's native per-step kernels in DESIGN §5
+        (profiles/r04c_lstm_miopen_vs_native.txt)."""
+        return self.lstm(x)[0]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = self.linear(self.lstm_out(x))

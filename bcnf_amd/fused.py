@@ -17,7 +17,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 from dataclasses import dataclass
 
 import torch
@@ -400,13 +399,13 @@ class FusedStack(StackBase):
         return N.query_status("bcnf_fold_bytes", self._pdesc, int(in_features))[0] == N.OK
 
     # bcnf_fold_train_forward (the pack-free folded forward, one launch) where its table applies; False: always the
-    # two-launch form (pack + fold, then the forward) -- BCNF_FOLD_RAW=0 in the environment, for A/B runs
-    use_raw_forward = os.environ.get("BCNF_FOLD_RAW", "1") != "0"
+    # two-launch form (pack + fold, then the forward), which tests and tools set on an instance as a reference
+    use_raw_forward = True
 
     def raw_table(self, X: int):
         """The device copy of bcnf_fold_raw_table for in_features X (built once per device), or None where the
-        pack-free forward does not apply (or the library predates it)."""
-        if not self.use_raw_forward or not hasattr(N.lib(), "bcnf_fold_train_forward"):
+        pack-free forward does not apply."""
+        if not self.use_raw_forward:
             return None
         dev = self.flat.device
         key = (X, str(dev))

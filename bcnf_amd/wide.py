@@ -10,7 +10,6 @@ one GEMM per pass.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
@@ -174,34 +173,18 @@ class WideStack(StackBase):
     # Data parallel (TrainStep): (bucket, offset) -- the coupling gradients land in bucket[offset:offset + n], a view
     # that autograd adopts as .grad; and, with range_blocks (descending real-block ranges covering [0, nb)), the
     # backward runs range by range and calls on_range(lo, hi) with each finished range's bucket slice [lo, hi), so
-    # the slice's all-reduce overlaps the rest of the backward (bcnf_wide_fold_backward_range).
+    # the slice's all-reduce overlaps the rest of the backward (one bcnf_wide_fold_backward call per range).
     grad_bucket = None
     range_blocks = None
     on_range = None
-    # TrainStep: with side_stream set, the coupling parameter gradients (bcnf_wide_fold_backward_phase 2) run on it
-    # while the rest of the backward (the feature network's, fed by dL/dx from phase 1) continues on the launch
-    # stream; join_side() makes the launch stream wait for them (before the gradients are read).
-    side_stream = None
-    _side_pending = None
-
-    def join_side(self, param=None):
-        """The launch stream waits for the side-stream parameter gradients of the last backward (no-op if none)."""
-        pend, self._side_pending = self._side_pending, None
-        if pend is None:
-            return
-        ev, stream, ptr, _keep = pend
-        stream.wait_event(ev)
-        if param is not None and param.requires_grad and (param.grad is None or param.grad.data_ptr() != ptr):
-            # autograd copied the gradient (a clone on the launch stream) instead of adopting the side-stream buffer
-            raise RuntimeError("bcnf_amd: the side-stream coupling gradient was not adopted as .grad")
 
     def block_offset(self, block: int) -> int:
         """Canonical flat offset of real block `block` (block = nb: the parameter count)."""
         return N.query_i64("bcnf_wide_block_offset", self._pdesc, block)
 
     def _fold_backward_args(self, z, dvals, saved, want_x):
-        """The arguments the three folded backward entry points share (all but the range / phase and the stream), the
-        gradient buffers among them: dparams is the bucket's slice in a data-parallel TrainStep."""
+        """bcnf_wide_fold_backward's arguments up to the block range and the stream, the gradient buffers among them:
+        dparams is the bucket's slice in a data-parallel TrainStep."""
         ws, pk, x1, wfb, wcb, xp, _ = saved
         B = z.shape[0]
         gx = torch.empty_like(wcb)
@@ -225,23 +208,10 @@ class WideStack(StackBase):
         if self.range_blocks and self.on_range is not None and self.grad_bucket is not None:
             off = self.grad_bucket[1]
             for lo, hi in self.range_blocks:
-                N.call("bcnf_wide_fold_backward_range", *args, lo, hi, stream)
+                N.call("bcnf_wide_fold_backward", *args, lo, hi, stream)
                 self.on_range(off + self.block_offset(lo), off + self.block_offset(hi))
-        elif self.side_stream is not None:
-            if self._side_pending is not None:
-                raise RuntimeError("bcnf_amd: a side-stream backward is still pending (join_side() not called)")
-            cur = torch.cuda.current_stream(dev)
-            N.call("bcnf_wide_fold_backward_phase", *args, 1, stream)
-            side = self.side_stream
-            side.wait_stream(cur)
-            N.call("bcnf_wide_fold_backward_phase", *args, 2, ctypes.c_void_p(side.cuda_stream))
-            ev = torch.cuda.Event()
-            ev.record(side)
-            # everything phase 2 reads stays alive until the join (freed afterwards on the launch stream, so a reuse
-            # is ordered after the side stream's work); dparams itself must be adopted as .grad, not copied
-            self._side_pending = (ev, cur, dparams.data_ptr(), (ws, pk, x1, wfb, wcb, z, dvals, gx, self.flat))
         else:
-            N.call("bcnf_wide_fold_backward", *args, stream)
+            N.call("bcnf_wide_fold_backward", *args, 0, self.cfg.n_blocks, stream)
         return dparams, dwfb[:, :X], dwfb[:, X], (dx[:, :X] if want_x else None)
 
     @torch.no_grad()
@@ -255,7 +225,7 @@ class WideStack(StackBase):
         else:
             forward, (z, _, saved) = self._fold_forward_call(y, *fold, training)
             args, _ = self._fold_backward_args(z, None, saved, want_x=True)
-            backward = ("bcnf_wide_fold_backward", *args, N.stream_handle(y.device))
+            backward = ("bcnf_wide_fold_backward", *args, 0, self.cfg.n_blocks, N.stream_handle(y.device))
         return self._time_calls({"forward": forward, "backward": backward}, iters)
 
     # ------------------------------------------------------------------ inverse (StackBase.launch_inverse)

@@ -59,9 +59,10 @@ extern "C" {
 
 #define BCNF_MAX_HIDDEN 8
 #define BCNF_MAX_TENSORS 48
-/* Layout version of the structs below (2: BcnfStackDesc.gemm_tiling appended). bcnf_abi_version() returns the
- * library's; a caller compares it with this macro before passing any struct. */
-#define BCNF_AMD_ABI_VERSION 2
+/* Version of the structs and signatures below (2: BcnfStackDesc.gemm_tiling appended; 3: bcnf_wide_fold_backward
+ * takes block_lo, block_hi, its _range and _phase variants are gone). bcnf_abi_version() returns the library's; a
+ * caller compares it with this macro before passing any struct. */
+#define BCNF_AMD_ABI_VERSION 3
 
 int bcnf_abi_version(void);
 
@@ -436,30 +437,17 @@ int bcnf_wide_fold_prepare(const BcnfStackDesc* desc, const void* packed, const 
 int bcnf_wide_fold_forward(const BcnfStackDesc* desc, const float* params, const void* packed, const float* y,
                            const float* x1, int32_t xp, const float* wcb, int64_t batch, float* z, float* ldj,
                            int32_t training, const uint64_t* rng_state, void* workspace, void* stream);
+/* The backward runs over real blocks [block_lo, block_hi); the whole backward is (0, nb). Data parallelism that
+ * overlaps the gradient exchange with the rest of the backward (trainer.py:244-277 is the single-process
+ * step it splits) makes one call per contiguous block range, in descending order over one forward's workspace, the
+ * first with block_hi = nb and the last with block_lo = 0. A call runs the backward chain until blocks
+ * [block_lo, block_hi) are complete and writes their canonical parameter gradients,
+ * dparams[bcnf_wide_block_offset(block_lo) .. bcnf_wide_block_offset(block_hi)); the block_lo = 0 call also writes
+ * dwfb and dx. Results equal the one (0, nb) call bit for bit; calls out of that order leave the outputs undefined. */
 int bcnf_wide_fold_backward(const BcnfStackDesc* desc, const float* params, const void* packed, const float* x1,
                             int32_t xp, const float* wfb, const float* wcb, const float* z, const float* dloss,
                             int64_t batch, void* workspace, float* gx_scratch, float* dparams, float* dwfb, float* dx,
-                            void* stream);
-/* bcnf_wide_fold_backward split over real blocks, for data parallelism that overlaps the gradient exchange with the
- * rest of the backward (trainer.py:244-277 is the single-process step it splits): one call per
- * contiguous block range [block_lo, block_hi), in descending order over one forward's workspace, the first with
- * block_hi = nb and the last with block_lo = 0. A call runs the backward chain until blocks [block_lo, block_hi) are
- * complete and writes their canonical parameter gradients, dparams[bcnf_wide_block_offset(block_lo) ..
- * bcnf_wide_block_offset(block_hi)); the block_lo = 0 call also writes dwfb and dx. Results equal one
- * bcnf_wide_fold_backward call bit for bit; calls out of that order leave the outputs undefined. */
-int bcnf_wide_fold_backward_range(const BcnfStackDesc* desc, const float* params, const void* packed, const float* x1,
-                                  int32_t xp, const float* wfb, const float* wcb, const float* z, const float* dloss,
-                                  int64_t batch, void* workspace, float* gx_scratch, float* dparams, float* dwfb,
-                                  float* dx, int32_t block_lo, int32_t block_hi, void* stream);
-/* bcnf_wide_fold_backward in two phases, for a caller that overlaps the coupling parameter gradients with the rest of
- * its own backward (the feature network's, trainer.py:244-277 runs both in one loss.backward()): phase 1 writes dx and
- * dwfb (and gx_scratch), phase 2 writes dparams; phase 2 must follow phase 1 in stream order (a second stream waiting
- * on an event recorded after phase 1 is the intended use) and both must finish before the next call on the same
- * workspace. phase 3 = both, one stream. Results equal one bcnf_wide_fold_backward call bit for bit. */
-int bcnf_wide_fold_backward_phase(const BcnfStackDesc* desc, const float* params, const void* packed, const float* x1,
-                                  int32_t xp, const float* wfb, const float* wcb, const float* z, const float* dloss,
-                                  int64_t batch, void* workspace, float* gx_scratch, float* dparams, float* dwfb,
-                                  float* dx, int32_t phase, void* stream);
+                            int32_t block_lo, int32_t block_hi, void* stream);
 /* Canonical flat offset of real block `block`'s first trainable parameter (its ActNorm, cnf.py:296-335 module order);
  * block = nb gives the parameter count. Host-only. */
 int bcnf_wide_block_offset(const BcnfStackDesc* desc, int32_t block, int64_t* offset);
@@ -804,7 +792,7 @@ int bcnf_lds_fill(float value, void* stream);
 int bcnf_wide_gemm_test(int32_t layout, int32_t M, int32_t N, int32_t K, const float* A, int64_t lda, const float* B,
                         int64_t ldb, float* C, int64_t ldc, void* stream);
 /* Test hook (host arithmetic only, no launch): the workspace / G-region plan of one folded wide backward call
- * (bcnf_wide_fold_backward_range) at `batch` rows over blocks [block_lo, block_hi), dL/dx and [dWf | dbf] wanted or
+ * (bcnf_wide_fold_backward) at `batch` rows over blocks [block_lo, block_hi), dL/dx and [dWf | dbf] wanted or
  * not: out[0] = training workspace floats, out[1] = offset of the G region in it, out[2] = G region floats, out[3] =
  * the feature-side split-K partials at the region's end, out[4] / out[5] = offset (within G) / floats of the range's
  * parameter-gradient split-K scratch, out[6] / out[7] = the dL/dx / [dWf | dbf] partial needs. Checked by

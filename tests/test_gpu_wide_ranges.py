@@ -1,5 +1,5 @@
-"""GPU tests of the range-split wide backward (bcnf_wide_fold_backward_range, WideStack.range_blocks): the folded
-wide backward run as descending real-block ranges, each range's coupling-gradient slice handed to a callback right
+"""GPU tests of the range-split wide backward (bcnf_wide_fold_backward over block ranges, WideStack.range_blocks): the
+folded wide backward run as descending real-block ranges, each range's coupling-gradient slice handed to a callback right
 after its launches (TrainStep.overlap_ranges all-reduces it there), must equal the one-call backward bit for bit
 (per output element the same GEMM K order; the split-K partials of a range use its own dead G slots) and every
 slice must be final when it is handed over. One-way (S = 1) and two_way (S = 2) stacks, ragged batch, dropout on
@@ -71,73 +71,31 @@ def test_range_backward_equals_one_call(two_way, ranges):
 
 def _cfg_deep(two_way):
     c = _cfg(two_way)
-    c["feature_networks"][1]["kwargs"]["sizes"] = [90, 64, 80]     # a layer below the folded Linear: its backward
-    return c                                                       # runs on the launch stream during phase 2
+    c["feature_networks"][1]["kwargs"]["sizes"] = [90, 64, 80]     # a layer below the folded Linear: dL/dx is wanted
+    return c
 
 
-def _side_grads(m, y, traj, side):
+PER_BLOCK = [(4, 5), (3, 4), (2, 3), (1, 2), (0, 1)]
+
+
+def _side_grads(m, y, traj, ranges=None):
+    """Coupling gradient, loss values and every feature-network gradient of one NLL step; ranges: the backward run
+    range by range into a bucket slice (the data-parallel hooks), else as one call."""
     st = m.fused
     m.zero_grad(set_to_none=True)
     st.flat_param.grad = None
     st.set_seed(7)
-    st.side_stream = side
+    if ranges is not None:
+        st.grad_bucket = (torch.full((st.flat.numel() + 9,), float("nan"), device=DEV), 5)
+        st.range_blocks = ranges
+        st.on_range = lambda lo, hi: None
     try:
         vals = m.nll_loss(y, traj)
         torch.autograd.backward(vals, torch.tensor([1.0, 0.0, 0.0], device=DEV))
     finally:
-        st.side_stream = None
-        st.join_side(st.flat_param)
+        st.grad_bucket = st.range_blocks = st.on_range = None
     return [st.flat_param.grad.clone(), vals.detach().clone()] + \
         [p.grad.clone() for p in m.feature_network_stack.parameters()]
-
-
-@pytest.mark.parametrize("two_way", [False, True], ids=["one_way", "two_way"])
-@pytest.mark.parametrize("B", [77, 1024])
-def test_side_stream_backward_equals_one_call(two_way, B):
-    """bcnf_wide_fold_backward_phase: phase 1 (chain, dL/dx, Gx, [dWf | dbf]) on the launch stream, phase 2 (the
-    coupling parameter gradients) on a side stream while the feature layer below the fold runs its backward: equal
-    to the one-call backward bit for bit, and the side buffer is what autograd adopted as .grad."""
-    from bcnf_amd import CondRealNVP_v2
-    from bcnf_amd.wide import WideStack
-    torch.manual_seed(3)
-    m = CondRealNVP_v2.from_config(_cfg_deep(two_way)).to(DEV).train()
-    m.flat_parameters()
-    assert isinstance(m.fused, WideStack)
-    g = torch.Generator().manual_seed(4)
-    y = torch.randn(B, 19, generator=g).to(DEV)
-    traj = torch.randn(B, 30, 3, generator=g).to(DEV)
-    ref = _side_grads(m, y, traj, None)
-    side = torch.cuda.Stream()
-    for _ in range(2):
-        got = _side_grads(m, y, traj, side)
-        torch.cuda.synchronize()
-        assert len(got) == len(ref)
-        for a, b in zip(ref, got):
-            assert torch.equal(a, b)
-
-
-def test_side_stream_trainstep_equals_single_stream(monkeypatch):
-    """TrainStep (captured) with the side-stream parameter gradients (BCNF_WIDE_SIDE=1) vs without: identical parameters after
-    three steps (the join precedes Adam in the graph)."""
-    from bcnf_amd import CondRealNVP_v2
-    from bcnf_amd.train import TrainStep
-    g = torch.Generator().manual_seed(5)
-    y = torch.randn(256, 19, generator=g).to(DEV)
-    traj = torch.randn(256, 30, 3, generator=g).to(DEV)
-    out = []
-    for side in ("1", "0"):
-        monkeypatch.setenv("BCNF_WIDE_SIDE", side)
-        torch.manual_seed(3)
-        m = CondRealNVP_v2.from_config(_cfg_deep(True)).to(DEV).train()
-        ts = TrainStep(m, capture=True)
-        assert (ts._side is not None) == (side == "1")
-        m.fused.set_seed(11)
-        vals = [ts.step(y, traj) for _ in range(3)]
-        torch.cuda.synchronize()
-        out.append((vals, [p.detach().clone() for p in m.parameters()]))
-    assert out[0][0] == out[1][0]
-    for a, b in zip(out[0][1], out[1][1]):
-        assert torch.equal(a, b)
 
 
 def _guarded_workspace(monkeypatch, st, guards):
@@ -165,7 +123,8 @@ def test_fold_backward_g_region_boundaries(monkeypatch, B):
     cover a tail that exceeds the region (must reserve nothing and run unsplit: a reservation of more than the region
     pointed BEFORE it, into the activation region the parameter gradients read), a tail that fills it exactly or
     nearly (the head partials get a region of ~0 floats) and the usual case. Checks: no write outside the workspace
-    (NaN canaries), phase 1 + phase 2 on two streams == one call bit for bit, folded == unfolded (rtol 1e-4)."""
+    (NaN canaries), per-block ranges (each range's parameter-gradient partials at the head of its own G slots) == one
+    call bit for bit, folded == unfolded (rtol 1e-4)."""
     from bcnf_amd import CondRealNVP_v2
     from bcnf_amd.wide import WideStack
     torch.manual_seed(3)
@@ -178,10 +137,11 @@ def test_fold_backward_g_region_boundaries(monkeypatch, B):
     g = torch.Generator().manual_seed(B)
     y = torch.randn(B, 19, generator=g).to(DEV)
     traj = torch.randn(B, 30, 3, generator=g).to(DEV)
-    one = _side_grads(m, y, traj, None)
-    two = _side_grads(m, y, traj, torch.cuda.Stream())
+    one = _side_grads(m, y, traj)
+    split = _side_grads(m, y, traj, PER_BLOCK)
     torch.cuda.synchronize()
-    for a, b in zip(one, two):
+    assert len(one) == len(split)
+    for a, b in zip(one, split):
         assert torch.equal(a, b)
     for buf in guards:
         gsz = 1 << 16
@@ -190,7 +150,7 @@ def test_fold_backward_g_region_boundaries(monkeypatch, B):
     m.fold_features = False
     try:
         assert m._wide_fold(y, (traj,)) is None
-        ref = _side_grads(m, y, traj, None)
+        ref = _side_grads(m, y, traj)
     finally:
         del m.fold_features
     assert torch.allclose(one[1], ref[1], rtol=2e-6, atol=1e-5)                  # the loss values

@@ -252,4 +252,4 @@ def test_header_and_exports_agree():
     assert {"bcnf_resim_error_median", "bcnf_resim_impacts"} <= declared
     lib = N.lib()
     assert hasattr(lib, "bcnf_resim_error_median") and hasattr(lib, "bcnf_resim_impacts")
-    assert "#define BCNF_AMD_ABI_VERSION 2\n" in src and N.ABI_VERSION == 2 == lib.bcnf_abi_version()
+    assert "#define BCNF_AMD_ABI_VERSION 3\n" in src and N.ABI_VERSION == 3 == lib.bcnf_abi_version()

@@ -10,8 +10,7 @@ LOG=${1:-profiles/r06_asan_host.txt}
 RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -Iinclude \
   -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer -Xarch_host -g \
-  bcnf_amd/csrc/bcnf_stack.hip bcnf_amd/csrc/bcnf_train.hip bcnf_amd/csrc/bcnf_wide.hip bcnf_amd/csrc/bcnf_eval.hip \
-  bcnf_amd/csrc/bcnf_resim.hip -o build_exp/libasan.so
+  bcnf_amd/csrc/bcnf_*.hip -o build_exp/libasan.so    # every unit: the bindings take every entry point of the header
 nm -D build_exp/libasan.so | grep -c " U __asan_" | sed 's/^/asan runtime references in the library: /' > "$LOG"
 {
   echo "runtime: $RT"

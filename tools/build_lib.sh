@@ -5,5 +5,4 @@ mkdir -p build_exp
 name=${1:-head}
 shift || true
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -Iinclude "$@" \
-  bcnf_amd/csrc/bcnf_stack.hip bcnf_amd/csrc/bcnf_train.hip bcnf_amd/csrc/bcnf_wide.hip bcnf_amd/csrc/bcnf_eval.hip \
-  bcnf_amd/csrc/bcnf_resim.hip -o build_exp/lib$name.so
+  bcnf_amd/csrc/bcnf_*.hip -o build_exp/lib$name.so    # every unit: the bindings take every entry point of the header

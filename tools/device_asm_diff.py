@@ -1,6 +1,7 @@
 """Are two builds' device code the same, kernel for kernel?  python tools/device_asm_diff.py DIR_A DIR_B
 
-DIR_A / DIR_B each hold bcnf_<unit>.s for the seven translation units of bcnf_amd/csrc, made on the two commits with
+DIR_A / DIR_B each hold bcnf_<unit>.s for every translation unit (bcnf_*.hip) of bcnf_amd/csrc, made on the two commits
+with
   hipcc --offload-arch=gfx950 -O3 -std=c++17 --offload-device-only -S -Iinclude bcnf_amd/csrc/bcnf_<unit>.hip -o DIR/bcnf_<unit>.s
 Each file is split at its function symbols (instantiation order may move between builds), then per unit: the sets of
 .amdhsa_kernel names are compared, and each function's text and each kernel's .amdhsa_* descriptor (registers, LDS,
@@ -8,11 +9,13 @@ scratch). Two things move with a function's position in the file and are normali
 (.LBB<function>_<block>: renumbered by first appearance inside the function) and the `;` comments that name them.
 Prints one line per unit; exit status 1 if anything differs.
 """
+import glob
 import os
 import re
 import sys
 
-UNITS = ("attn", "eval", "head", "resim", "stack", "train", "wide")
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir, "bcnf_amd", "csrc")
+UNITS = tuple(sorted(os.path.basename(p)[5:-4] for p in glob.glob(os.path.join(CSRC, "bcnf_*.hip"))))
 
 
 def split(path):

@@ -21,8 +21,7 @@ def main():
     x = torch.randn(B, 90, device="cuda")
     lin = m.feature_network_stack.feature_networks[1].nn[0]
     t = m.fused.time_kernels(y, None, training=True, iters=50, fold=(x, lin.weight.detach(), lin.bias.detach()))
-    print(os.environ.get("BCNF_AMD_LIB", "default"), os.environ.get("BCNF_FOLD_RAW", "1"),
-          {k: round(v, 2) for k, v in t.items()})
+    print(os.environ.get("BCNF_AMD_LIB", "default"), {k: round(v, 2) for k, v in t.items()})
     L = N.lib()
     if hasattr(L, "bcnf_debug_phases"):
         buf = (ctypes.c_ulonglong * 32)()
