@@ -11,6 +11,7 @@ results agree to rounding. Pinned against fixtures produced by running the refer
 
 Reference anchors:
   * nested MLP            cnf.py:49-107   (Linear → GELU(erf) → Dropout …, final Linear; t, tanh(s))
+  * variant MLP layers    layers.py:9-78  (AnyGLU; LinearFFTEnriched = Linear over cat(x, Re rfft x, Im rfft x))
   * affine coupling       cnf.py:165-213  (forward, and the (non-inverse for two_way) inverse)
   * orthonormal mix       cnf.py:312-339  (y @ Q, inverse z @ Q.T)
   * ActNorm               cnf.py:342-354  (scale*x + bias, log|scale| summed; inverse divides)
@@ -42,6 +43,11 @@ class StackSpec:
     # LSTM feature net (feature_network.py:148-178); lstm = (input_size, hidden_size, num_layers, bidirectional,
     # pool_dim) replaces the FullyConnected one when set
     lstm: tuple | None = None
+    # the nested MLP's layer (layers.py:9-78): "Linear", "LinearFFTEnriched" or "AnyGLU" (gate `glu_activation`, a
+    # torch.nn module name: layer_kwargs["activation"]), and the activation between layers: "GELU" or "Identity"
+    layer: str = "Linear"
+    glu_activation: str = "GELU"
+    activation: str = "GELU"
 
     @property
     def Da(self):
@@ -71,6 +77,31 @@ def mlp_linear_indices(spec: StackSpec):
     return [i * stride for i in range(n)]
 
 
+def mlp_layer(sd, key, spec, x):
+    """One layer of the nested MLP (cnf.py:79-85 builds it through LayerFactory) under the state_dict prefix `key`:
+    nn.Linear, or one of the variant layers of layers.py."""
+    if spec.layer == "Linear":
+        return F.linear(x, sd[key + ".weight"], sd[key + ".bias"])
+    if spec.layer == "LinearFFTEnriched":                             # layers.py:60-78
+        f = torch.fft.rfft(x, dim=-1, norm="forward")                 # layers.py:42
+        x = torch.cat((x, f.real, f.imag), dim=-1)                    # layers.py:45, 57
+        return F.linear(x, sd[key + ".linear.weight"], sd[key + ".linear.bias"])
+    if spec.layer == "AnyGLU":                                        # layers.py:9-31
+        gate = F.linear(x, sd[key + ".linear_gate.weight"], sd[key + ".linear_gate.bias"])
+        value = F.linear(x, sd[key + ".linear_value.weight"], sd[key + ".linear_value.bias"])
+        return value * getattr(torch.nn, spec.glu_activation)()(gate)  # layers.py:31
+    raise NotImplementedError(f"oracle: layer {spec.layer!r}")
+
+
+def mlp_activation(spec, x):
+    """The module between two layers (cnf.py:82, LayerFactory.get_layer(activation))."""
+    if spec.activation == "GELU":
+        return F.gelu(x)                                              # nn.GELU(), approximate='none'
+    if spec.activation == "Identity":
+        return x
+    raise NotImplementedError(f"oracle: activation {spec.activation!r}")
+
+
 def nested_mlp(sd, prefix, spec, y, h, training, gen=None, keep=None):
     """ConditionalNestedNeuralNetwork.forward (cnf.py:98-107). Training-mode dropout masks: nn.Dropout's own draw by
     default, torch.rand masks from `gen`, or masks from outside -- `keep(li)` returns the bool [B, width] keep mask of
@@ -80,9 +111,9 @@ def nested_mlp(sd, prefix, spec, y, h, training, gen=None, keep=None):
     idx = mlp_linear_indices(spec)
     x = y
     for li, i in enumerate(idx):
-        x = F.linear(x, sd[f"{prefix}.nn.{i}.weight"], sd[f"{prefix}.nn.{i}.bias"])
+        x = mlp_layer(sd, f"{prefix}.nn.{i}", spec, x)
         if li < len(idx) - 1:
-            x = F.gelu(x)                                             # nn.GELU(), approximate='none'
+            x = mlp_activation(spec, x)
             if spec.dropout > 0.0 and training:
                 if keep is not None:
                     x = x * keep(li).to(x.dtype) / (1.0 - spec.dropout)

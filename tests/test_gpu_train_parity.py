@@ -415,13 +415,12 @@ def wide_case(name):
     return case
 
 
-@pytest.mark.parametrize("name", list(WIDE))
-def test_wide_record_masks_are_independent_draws(name):
+def assert_record_masks_are_independent_draws(case):
     """The masks read from the records: the dropped fraction is within 4 sigma of p (a kept unit whose fp32 activation
     and factor are both exactly zero reads as dropped: no room for many of those), every pair of distinct (block,
     half, layer) masks of the launch agrees at the rate of independent draws, (1 - p)^2 + p^2 within 4 sigma (a tag
-    collision would make two of them equal), and the next offset draws other masks."""
-    case = wide_case(name)
+    collision would make two of them equal), and the next offset draws other masks. `case`: a wide-family case with
+    its `masks` read at OFFSET (wide_case here; the LinearFFTEnriched cases of tests/test_gpu_variants_fp64.py)."""
     p = float(np.float32(case.spec.dropout))
     k = case.masks.flatten(0, 1)                           # [nv * NH][B][H]
     n = k[0].numel()
@@ -437,6 +436,12 @@ def test_wide_record_masks_are_independent_draws(name):
     a2 = (nxt == case.masks).double().mean().item()
     assert abs(a2 - q) <= 4 * np.sqrt(q * (1 - q) / k.numel()), (a2, q)
     assert torch.equal(_wide_records(case, OFFSET), case.masks)       # and the same offset the same ones
+
+
+@pytest.mark.parametrize("name", list(WIDE))
+def test_wide_record_masks_are_independent_draws(name):
+    """assert_record_masks_are_independent_draws at every wide case."""
+    assert_record_masks_are_independent_draws(wide_case(name))
 
 
 WIDE_PATHS = [(n, p) for n in WIDE for p in ("unfused", "fused") + (("folded",) if WIDE[n][1] else ())]

@@ -85,9 +85,9 @@ def test_variant_gradients_match_reference(name):
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_variant_training_loss_paths_agree(name):
-    """Training mode (dropout on): the fused / layerwise NLL (model.nll_loss, the Trainer's loss) and the
-    forward + inn_nll_loss give gradients of the same size; the loss is finite and the masks change per call."""
-    from bcnf_amd import inn_nll_loss
+    """Training mode (dropout on): the fused / layerwise NLL (model.nll_loss, the Trainer's loss) is finite with
+    loss == nll and mse == 0, its gradients are finite and not all zero, and the masks change per call. The numbers
+    are compared with the fp64 oracle under the launch's own masks in tests/test_gpu_variants_fp64.py."""
     m, d = _model(name)
     m.train()
     y, c = torch.from_numpy(d["y"]).to(DEV), torch.from_numpy(d["cond"]).to(DEV)
@@ -100,7 +100,6 @@ def test_variant_training_loss_paths_agree(name):
         z1 = m.forward(y, c)
         z2 = m.forward(y, c)
     assert not torch.equal(z1, z2)
-    _ = inn_nll_loss
 
 
 def test_fft_sampling_runs_on_the_wide_kernels():

@@ -1,5 +1,6 @@
 """Pin the CPU oracle (oracle/cnf_oracle.py) against fixtures produced by running the reference itself."""
 import numpy as np
+import pytest
 import torch
 
 from conftest import close, golden_sd, load_golden
@@ -66,6 +67,41 @@ def test_oracle_two_way_matches_reference():
     assert close(inv, d["inv"], 1e-6, 1e-6)[0]
     # the two_way "inverse" is not the inverse: the reference's own round trip error is large
     assert float((inv - torch.from_numpy(d["x"])).abs().max()) > 1e-4
+
+
+VARIANT_FIXTURES = {
+    "g12_fft_enriched.npz": O.StackSpec(size=19, nested_sizes=[40] * 3, n_blocks=3, n_conditions=12, dropout=0.407,
+                                        act_norm=True, layer="LinearFFTEnriched"),
+    "g13_anyglu.npz": O.StackSpec(size=19, nested_sizes=[24] * 3, n_blocks=3, n_conditions=12, dropout=0.407,
+                                  act_norm=True, two_way=True, layer="AnyGLU", glu_activation="Sigmoid"),
+}
+
+
+@pytest.mark.parametrize("fixture", sorted(VARIANT_FIXTURES))
+def test_oracle_variant_layers_match_reference(fixture):
+    """The oracle's LinearFFTEnriched (torch.fft.rfft, not the package's rfft matrix) and AnyGLU layers in float64
+    against the reference's own eval-mode outputs and autograd gradients (g12: FFT, one-way; g13: AnyGLU with a
+    Sigmoid gate, two_way, the bug-compatible inverse included): z, ldj, inverse, loss and every grad/* entry at this
+    file's gate without its relative term, |err| <= 1e-6 max(1, max|ref|). The fixtures are fp32 results, so what is
+    left is their own rounding: z 1.9e-7 / 1.7e-7, ldj 1.2e-7, inverse 1.7e-7 / 2.6e-7, worst gradient 1.4e-7 /
+    1.6e-7 of that scale."""
+    d = load_golden(fixture)
+    spec = VARIANT_FIXTURES[fixture]
+    sd = {k: v.double().requires_grad_(not k.endswith("orthonormal_matrix")) for k, v in golden_sd(d).items()}
+    y, c = torch.from_numpy(d["y"]).double(), torch.from_numpy(d["cond"]).double()
+    z, ldj = O.model_forward(sd, spec, y, c)
+    loss = O.inn_nll_loss(z, ldj)
+    loss.backward()
+    with torch.no_grad():
+        inv = O.model_inverse(sd, spec, torch.from_numpy(d["z"]).double(), c)
+    for key, got in (("z", z), ("ldj", ldj), ("inv", inv), ("loss", loss)):
+        ok, err = close(got.detach(), d[key], rtol=0.0, floor=1e-6)
+        assert ok, (fixture, key, err)
+    grads = [k for k in d.keys() if k.startswith("grad/")]
+    assert sorted(k[5:] for k in grads) == sorted(k for k, v in sd.items() if v.requires_grad)
+    for k in grads:
+        ok, err = close(sd[k[5:]].grad, d[k], rtol=0.0, floor=1e-6)
+        assert ok, (fixture, k, err)
 
 
 def test_orthonormal_regeneration_bit_exact_on_this_host():
