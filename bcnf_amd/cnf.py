@@ -6,7 +6,7 @@ state_dict keys are those of the reference, so checkpoints load in both directio
 
 * `CondRealNVP_v2.forward / inverse / sample / log_prob` run the whole coupling stack (ActNorm,
   nested MLP, affine coupling, log|det J|, orthonormal mix) in ONE fused HIP launch
-  (bcnf_amd/csrc/bcnf_stack.hip, via the C-ABI in include/bcnf_amd.h); the backward is one more launch
+  (bcnf_amd/csrc/bcnf_stack_fwd.hip / bcnf_stack_inv.hip, via the C-ABI in include/bcnf_amd.h); the backward is one more launch
   plus a deterministic gradient reduction.
 * A standalone `ConditionalAffineCouplingLayer` runs on the same kernels (a one-block stack).
 * The feature networks stay PyTorch-ROCm (north star); their output h is the stack's input.

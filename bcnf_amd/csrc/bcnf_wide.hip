@@ -1952,7 +1952,7 @@ __global__ __launch_bounds__(WWG) void k_wactnorm_grad(const WideLayout L, const
 }
 
 // Mean of the per-sample NLL terms -> [loss, nll, mse = 0] (trainer.py:260-266) plus the dropout RNG advance and
-// the divergence guard, exactly as bcnf_stack.hip's nll_finalize (include/bcnf_amd.h, BCNF_GUARD_*).
+// the divergence guard, exactly as bcnf_stack_rec.h's nll_finalize (include/bcnf_amd.h, BCNF_GUARD_*).
 __global__ __launch_bounds__(WWG) void k_wnll_finalize(const float* __restrict__ part, long long B, float* __restrict__ out,
                                                        uint64_t* rng, int32_t* guard) {
   __shared__ float red[WWG];

@@ -1,6 +1,6 @@
 """Host runtime of the fused HIP coupling stack: flat parameter storage, packing, workspaces and the
 autograd boundary. PyTorch provides device memory, streams and autograd plumbing; all arithmetic of
-the coupling stack runs in libbcnf_amd.so (bcnf_amd/csrc/bcnf_stack.hip).
+the coupling stack runs in libbcnf_amd.so (bcnf_amd/csrc/bcnf_stack*.hip; the file map: bcnf_stack_internal.h).
 
 Parameter storage
 -----------------
@@ -16,7 +16,6 @@ per-layer `.grad` tensors as views of that flat gradient.
 from __future__ import annotations
 
 import ctypes
-import math
 from dataclasses import dataclass
 
 import torch
@@ -278,7 +277,7 @@ class StackBase:
 
 
 class FusedStack(StackBase):
-    """The register-resident small family: drives the HIP kernels of bcnf_stack.hip. A training launch is built by a
+    """The register-resident small family: drives the HIP kernels of bcnf_stack*.hip. A training launch is built by a
     `_*_call(s)` method, which validates, allocates and returns ((entry point, *arguments), results); `launch_*` runs
     it and `time_kernels` times the same tuples."""
 
@@ -522,15 +521,8 @@ class FusedStack(StackBase):
                rng, scratch, N.stream_handle(z.device))
 
     def _native_inverse_logdet(self, z, h, cond_index, y, training, ldj, logp, scratch):
-        rc = N.call_raw("bcnf_stack_inverse_logdet", self._pdesc, self.packed(), z, h, h.shape[0], cond_index,
-                           z.shape[0], y, ldj, logp, scratch, N.stream_handle(z.device))
-        if rc == N.ERR_UNSUPPORTED:
-            # a layout outside the matrix-core inverse: the plain inverse, then the forward kernels at y
-            y = self.launch_inverse(z, h, cond_index, training)
-            hh = h if cond_index is None else h.index_select(0, cond_index)
-            _, ldj, _, _ = self.launch_forward(y, hh.contiguous(), False, save=False)
-            return y, ldj, log_prob_of_latent(z, ldj)
-        N.check(rc, "bcnf_stack_inverse_logdet")
+        N.call("bcnf_stack_inverse_logdet", self._pdesc, self.packed(), z, h, h.shape[0], cond_index, z.shape[0], y,
+               ldj, logp, scratch, N.stream_handle(z.device))
         return y, ldj, logp
 
 
@@ -737,11 +729,6 @@ def stack_nll_fold(stack: FusedStack, y, x, wf, bf, training: bool, defer: bool 
     if torch.is_grad_enabled() and (params_grad or feat_grad):
         return _FoldNLL.apply(y, x, wf, bf, fp if params_grad else fp.detach(), stack, training, defer, gather)
     return stack.launch_fold_nll_forward(y, x, wf, bf, training, gather=gather)[2]
-
-
-def log_prob_of_latent(z, ldj):
-    """-0.5 |z|^2 + ldj - D/2 log 2pi (utils.log_prob_from_latent) for the composed fall-back."""
-    return -0.5 * z.pow(2).sum(dim=-1) + ldj - 0.5 * z.shape[-1] * math.log(2.0 * math.pi)
 
 
 class _StackInverse(torch.autograd.Function):

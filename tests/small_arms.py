@@ -1,11 +1,11 @@
-"""The host dispatch of the register-resident coupling family (bcnf_stack.hip) restated in plain Python: which template
-arm a (shape, mode, path) launches -- fwd_dispatch, bwd_dispatch, inv_dispatch, inv_ldj_dispatch, vec_rows,
+"""The host dispatch of the register-resident coupling family (bcnf_stack*.hip) restated in plain Python: which template
+arm a (shape, mode, path) launches -- launch_forward, launch_backward, launch_inverse, launch_inverse_logdet, vec_rows,
 raw_applicable with build_raw_table's capacity checks, and the record sizes of make_layout / round_rec they rest on.
 No GPU and no library: tests/test_small_arms_cpu.py holds the restatement to the library's own statuses and table, and
 holds the GPU files' case lists (imported in runs()) to the arm set and the branch registry below.
 
 NH is the parameter the kernels' compile-time schedules hang on (ActRec<NH>, rf_stage_q<NH>, BwdJobs<NH>, the two
-dropout float4, the backward's derivative slot), so every BCNF_CASE(N) arm is different code. A new arm or branch is
+dropout float4, the backward's derivative slot), so every arm of dispatch_nh is different code. A new arm or branch is
 registered HERE, and the census then fails until a case of the GPU lists reaches it."""
 from collections import namedtuple
 
@@ -65,10 +65,10 @@ def perm(L):
 
 
 def inv_dispatch(L, training):
-    """k_inverse<NH, true> where masks are drawn, else the matrix-core inverse k_inverse_mfma<NH, PERM, false> (every
-    layout make_layout produces has the record size and PMB the kernel's compile-time offsets assume)."""
+    """k_inverse<NH> where masks are drawn, else the matrix-core inverse k_inverse_mfma<NH, PERM, false> (layout_matches
+    holds the record size and PMB of every layout to the kernel's compile-time offsets)."""
     if training and L.p > 0.0:
-        return ("k_inverse", L.NH, True)
+        return ("k_inverse", L.NH)
     return ("k_inverse_mfma", L.NH, perm(L), False)
 
 
@@ -170,7 +170,7 @@ def required_arms():
     need = set()
     for NH in range(1, MAX_HIDDEN + 1):
         need |= {("k_forward", NH, d, s, False) for d in (False, True) for s in (False, True)}
-        need |= {("k_backward", NH), ("k_inverse", NH, True)}
+        need |= {("k_backward", NH), ("k_inverse", NH)}
         if NH >= 5:                  # the pack-free form; its table also builds at NH < 5, where no GPU case runs it yet
             need |= {("k_forward", NH, d, True, True) for d in (False, True)}
     return need

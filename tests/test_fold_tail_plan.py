@@ -5,7 +5,7 @@ import ctypes
 
 import pytest
 
-RED_FLOATS = 4 * 32           # slab floats per reduce workgroup (RED_O4 float4, bcnf_stack.hip)
+RED_FLOATS = 4 * 32           # slab floats per reduce workgroup (RED_O4 float4, bcnf_stack_tail.hip)
 
 # (nested_sizes, n_blocks, n_conditions, in_features)
 DESCS = {

@@ -13,7 +13,7 @@ from dropout_ref import SMALL_TRAIN_SHAPES, keep_bits, launch_sample, shape_conf
 pytestmark = pytest.mark.gpu
 
 
-def _sample_of(t):                      # bcnf_stack.hip sample_of: thread -> sample within the workgroup's 16
+def _sample_of(t):                      # bcnf_stack_layout.h sample_of: thread -> sample within the workgroup's 16
     return (t >> 6) + 4 * ((t >> 4) & 3)
 
 
@@ -71,7 +71,7 @@ def test_forward_dropout_masks_at_the_parity_shapes(case):
     every NH = 1 .. 8; a folded shape on its stack alone), ragged B = 37: every unit of the real lanes of all 16 rows
     of each workgroup, the 11 rows past the batch included (they replay sample B - 1, masks and all). Records:
     [k][workgroup][AR4][256 threads] float4, AR4 = (2 NH + 3) / 4, floats (activation, derivative) of hidden layers
-    1..NH first (ActRec, bcnf_stack.hip)."""
+    1..NH first (ActRec, bcnf_stack_rec.h)."""
     from bcnf_amd import CondRealNVP_v2
     cfg = _small_train_cases()[case]
     kw = cfg["model"]["kwargs"]

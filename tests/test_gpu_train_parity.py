@@ -5,7 +5,7 @@ graph vs eager) or one central difference along the gradient, so an error shared
 the gradient, passes. Here the oracle (oracle/cnf_oracle.py, float64, autograd) runs the same operation with the masks
 the launch drew, handed in through its `keep` hook:
 
-  * small family (bcnf_stack.hip k_forward / k_backward / k_inverse, folded tail): the masks come from the host
+  * small family (bcnf_stack*.hip k_forward / k_backward / k_inverse, folded tail): the masks come from the host
     restatement of the draw (tests/dropout_ref.py keep_callable; pinned bit for bit against the saved records at these
     shapes by tests/test_gpu_dropout.py), at the launch's (seed, offset) read from rng_state();
   * wide family (bcnf_wide.hip): the masks are read from the saved records of one forward launch at the same
@@ -33,7 +33,7 @@ from oracle import cnf_oracle as O
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-INV_TAG = 0x40000000          # k_inverse<NH, true>'s draw tag (bcnf_stack.hip)
+INV_TAG = 0x40000000          # k_inverse<NH>'s draw tag (bcnf_stack_inv.hip)
 OFFSET = 3                    # the Philox offset every compared launch runs at
 VAL = dict(rtol=1e-5, floor=1e-5)
 GRAD = dict(rtol=1e-4, floor=1e-4)
@@ -307,7 +307,7 @@ TRAIN_INVERSE = [("fc_small", 1, 1e-5), ("fc_small", 37, 1e-5), ("d7_h12_9", 1, 
 
 @pytest.mark.parametrize("name,B,tol", TRAIN_INVERSE)
 def test_small_training_mode_inverse_vs_fp64_oracle(name, B, tol):
-    """model.train(); model.inverse(): k_inverse<NH, true>, masks drawn with tag 0x40000000, at every NH = 1 .. 8. Gate
+    """model.train(); model.inverse(): k_inverse<NH>, masks drawn with tag 0x40000000, at every NH = 1 .. 8. Gate
     as the eval inverse test of the shape (test_ragged_batches_vs_oracle: 1e-5; test_other_shapes_vs_oracle: 1e-4);
     1e-5 at the shapes with a gain and at d32_nh1."""
     case = small_case(name, 37)
@@ -330,7 +330,7 @@ def test_small_training_mode_inverse_vs_fp64_oracle(name, B, tol):
 
 
 def test_small_training_mode_sample_vs_fp64_oracle():
-    """sample(outer=True) of a model left in train mode: the cond_index path of k_inverse<NH, true>, four launches
+    """sample(outer=True) of a model left in train mode: the cond_index path of k_inverse<NH>, four launches
     (conditions 4 + 3, samples 3 + 2), each at its own offset; the oracle draws the same CPU z stream by seeding."""
     case = small_case("fc_small", 37)
     m, st, spec = case.m, case.m.fused, case.spec
