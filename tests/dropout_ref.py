@@ -5,7 +5,10 @@ in-kernel generator can reproduce, so training parity is gated against the fp64 
 (keep_callable below hands them over). This module pins the kernel's own stream bit for bit:
 Philox4x32-10 (Salmon et al. 2011, checked against the Random123 known-answer vectors in tests/test_dropout_rule.py)
 and the keep rule "u32 >= round(p 2^32)". feature_keep restates the feature-MLP layers' draw (k_lin / k_gemm) the same
-way, for the fp64 oracle of tests/test_gpu_linear.py.
+way, for the fp64 oracle of tests/test_gpu_linear.py. wide_keep_bits restates the wide family's two draw rules
+(bcnf_wide.hip: drop4 in the link kernels, epi_rnd / epi4 in the chain GEMM's epilogue) and its truncating threshold;
+tests/test_gpu_wide_dropout.py holds every mask of a launch to it, and wide_keep_callable feeds the fp64 oracle of
+tests/test_gpu_train_parity.py.
 """
 import numpy as np
 
@@ -97,6 +100,65 @@ def feature_keep(p, seed, offset, salt, rows, cols):
     words = philox4x32_10(col, quad, offset & 0xFFFFFFFF, offset >> 32, k0, k1)      # four [quads, cols]
     u = np.stack([np.broadcast_to(w, (quads, cols)) for w in words], axis=1).reshape(4 * quads, cols)[:rows]
     return u >= np.uint64(thresh32(p))
+
+
+# ------------------------------------------------------------------------------------------ wide family
+# bcnf_wide.hip draws with two rules, both keyed (seed low, seed high ^ offset high) and both "keep iff u32 >= thresh":
+#   layer 0 (the link kernels, drop4):      unit (row b, hidden unit c) is word c & 3 of the draw with counter
+#                                           (b, (c & ~3) | 0x80000000, 16 v, offset low);
+#   layers 1 .. NH - 1 (the chain GEMM's EPI_ACT epilogue, epi_rnd / epi4; tag set in hidden_fwd):
+#                                           unit (row b, column c) is word b & 3 of the draw with counter
+#                                           (b & ~3, c, 16 v + l, offset low).
+# v is the virtual block (real block * S + side, S = 2 for two_way); BCNF_MAX_HIDDEN = 8 < 16, so no two tags meet.
+# Every EPI_ACT instance holds its accumulators in groups of four consecutive rows that start at a multiple of 4, so
+# the draw is a function of (seed, offset, v, l, b, c) alone, whatever GEMM tiling the dispatcher picks. The forward
+# (saving or not, folded or not) and wide_inverse use the same tags; the inverse's rows are the latent rows.
+def wide_thresh32(p):
+    """(uint32_t)((double)float32(p) 2^32), clamped to 2^32 - 1 (wide_layout in bcnf_wide.hip): truncation, where the
+    small family's thresh32 rounds to nearest. The two differ only for p < 2^-8, where float32(p) 2^32 has a
+    fractional part."""
+    t = float(np.float32(p)) * 4294967296.0                 # exact in binary64: a 24-bit significand times 2^32
+    return 0xFFFFFFFF if t >= 4294967295.0 else int(t)
+
+
+def wide_keep_bits(p, seed, offset, v, l, rows, H):
+    """bool [rows, H]: the keep mask of hidden layer l (0 .. NH - 1) of virtual block v in one wide-family launch of
+    `rows` rows at (seed, offset)."""
+    seed, offset = int(seed) & (2**64 - 1), int(offset) & (2**64 - 1)
+    assert 0 <= l < 16 and v >= 0 and rows >= 0 and H >= 0
+    k0, k1 = seed & 0xFFFFFFFF, ((seed >> 32) ^ (offset >> 32)) & 0xFFFFFFFF
+    olo = offset & 0xFFFFFFFF
+    if l == 0:
+        quads = (H + 3) // 4
+        b = np.arange(rows, dtype=np.uint64)[:, None]
+        c4 = (np.arange(quads, dtype=np.uint64)[None, :] * np.uint64(4)) | np.uint64(0x80000000)
+        words = philox4x32_10(b, c4, 16 * v, olo, k0, k1)                        # four [rows, quads]
+        u = np.stack([np.broadcast_to(w, (rows, quads)) for w in words], axis=2).reshape(rows, 4 * quads)[:, :H]
+    else:
+        quads = (rows + 3) // 4
+        b4 = np.arange(quads, dtype=np.uint64)[:, None] * np.uint64(4)
+        c = np.arange(H, dtype=np.uint64)[None, :]
+        words = philox4x32_10(b4, c, 16 * v + l, olo, k0, k1)                    # four [quads, H]
+        u = np.stack([np.broadcast_to(w, (quads, H)) for w in words], axis=1).reshape(4 * quads, H)[:rows]
+    return u >= np.uint64(wide_thresh32(p))
+
+
+def wide_keep_callable(p, seed, offset, n_blocks, two_way, hidden, rows):
+    """The oracle's `keep` callable (oracle/cnf_oracle.py: model_forward / model_inverse / sample) for one wide-family
+    launch of `rows` rows: keep(k, half, li) = bool [rows, hidden[li]] of virtual block v = k S + (half == "b"). Each
+    mask is formed on first use and kept."""
+    import torch
+    hidden = list(hidden)
+    S = 2 if two_way else 1
+    cache = {}
+
+    def keep(k, half, li):
+        assert 0 <= k < n_blocks and half in ("a", "b")[:S] and 0 <= li < len(hidden)
+        v = k * S + (half == "b")
+        if (v, li) not in cache:
+            cache[v, li] = torch.from_numpy(wide_keep_bits(p, seed, offset, v, li, rows, hidden[li]))
+        return cache[v, li]
+    return keep
 
 
 # The small-family (register-resident k_forward / k_backward / k_inverse) shapes the training-parity tests use besides

@@ -8,10 +8,12 @@ the launch drew, handed in through its `keep` hook:
   * small family (bcnf_stack*.hip k_forward / k_backward / k_inverse, folded tail): the masks come from the host
     restatement of the draw (tests/dropout_ref.py keep_callable; pinned bit for bit against the saved records at these
     shapes by tests/test_gpu_dropout.py), at the launch's (seed, offset) read from rng_state();
-  * wide family (bcnf_wide.hip): the masks are read from the saved records of one forward launch at the same
-    (seed, offset) -- a unit is kept iff its masked activation or derivative factor is nonzero. They come from the code
-    under test, so the forward comparison is what ties them to the masks applied; two independence checks and the zero
-    fraction keep a tag collision or a degenerate read from hiding behind them.
+  * wide family (bcnf_wide.hip): the masks come from the host restatement of its two draw rules
+    (tests/dropout_ref.py wide_keep_callable; pinned bit for bit against the saved records of every launch form by
+    tests/test_gpu_wide_dropout.py), at the launch's (seed, offset). The masks read from the records (a unit is kept
+    iff its masked activation or derivative factor is nonzero) remain for the independence checks only. The forward
+    that saves nothing, the training-mode inverse and sample(outer=True) in train mode, which leave no records, are
+    compared with the oracle under the restated masks as well.
 
 Gates (the eval-mode gates of tests/test_gpu_parity.py / test_gpu_wide.py; dropout adds one fp32 multiply per unit):
 z and log|det J| `close` at 1e-5, the loss 1e-5 |ref| + 1e-5, every parameter gradient, dL/dh and dL/dy
@@ -27,7 +29,7 @@ import torch
 
 from conftest import FC_SMALL_CFG, close, golden_sd, load_golden
 from dropout_ref import (SMALL_TRAIN_FOLD_X, SMALL_TRAIN_GAIN, SMALL_TRAIN_RAW, SMALL_TRAIN_SHAPES, apply_gain, fold_config,
-                         keep_callable, shape_config)
+                         keep_callable, shape_config, wide_keep_callable)
 from oracle import cnf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -363,16 +365,20 @@ WIDE = {
 }
 
 
-def _wide_records(case, offset):
-    """bool [nv][NH][B][H] on the device: unit kept iff its saved masked activation (A) or masked derivative factor
-    (G) of one saving forward launch at `offset` is nonzero. Offsets as carve() in bcnf_wide.hip: P (B nv HP), nllp
+# Not in WIDE (the training-step and independence tests keep their cases): the edge shape of the mask and inverse
+# tests. NH = 8 reaches the largest draw tag; H = 150 > 128 gives every GEMM tiling at least two column tiles and a
+# ragged last one; B = 131 two 128-row tiles and, 131 % 4 = 3, a ragged last row group.
+WIDE_EDGE = {
+    "w150_nh8": (dict(size=19, nested_sizes=[150] * 8, n_blocks=2, n_conditions=24, dropout=0.5, act_norm=True), None, 131),
+}
+
+
+def _workspace_records(ws, spec, B):
+    """bool [nv][NH][B][H] on the device from a saving wide launch's workspace: unit kept iff its saved masked
+    activation (A) or masked derivative factor (G) is nonzero. Offsets as carve() in bcnf_wide.hip: P (B nv HP), nllp
     (B), A, G (nv NH B HP each), every region padded to 4 floats plus 64."""
-    m, st, s = case.m, case.m.fused, case.spec
-    st.rng_state()[1] = offset
-    with torch.no_grad():
-        h = m.feature_network_stack(case.cond.to(DEV))
-        _, _, _, (ws, _) = st.launch_forward(case.y.to(DEV), h, True, save=True)
-    B, nv, NH, H = case.y.shape[0], s.n_blocks * (2 if s.two_way else 1), len(s.nested_sizes), s.nested_sizes[0]
+    s = spec
+    nv, NH, H = s.n_blocks * (2 if s.two_way else 1), len(s.nested_sizes), s.nested_sizes[0]
     HP = (H + 1 + 3) // 4 * 4
     pad = lambda n: (n + 3) // 4 * 4 + 64  # noqa: E731
     n = nv * NH * B * HP
@@ -383,10 +389,31 @@ def _wide_records(case, offset):
     return (A != 0) | (G != 0)
 
 
-@functools.lru_cache(maxsize=None)
-def wide_case(name):
+def _wide_records(case, offset):
+    """_workspace_records of one saving forward launch of the case at `offset`."""
+    m, st = case.m, case.m.fused
+    st.rng_state()[1] = offset
+    with torch.no_grad():
+        h = m.feature_network_stack(case.cond.to(DEV))
+        _, _, _, (ws, _) = st.launch_forward(case.y.to(DEV), h, True, save=True)
+    return _workspace_records(ws, case.spec, case.y.shape[0])
+
+
+def wide_seed(case):
+    """The launch's Philox seed, read from the device state as the launch reads it."""
+    return int(case.m.fused.rng_state()[0].item())
+
+
+def wide_keep(case, offset, rows):
+    """The oracle's `keep` for a launch of `rows` rows of the case at `offset`, from the host restatement of both wide
+    draw rules (tests/dropout_ref.py): nothing of it comes from the code under test but the seed it was handed."""
+    s = case.spec
+    return wide_keep_callable(s.dropout, wide_seed(case), offset, s.n_blocks, s.two_way, s.nested_sizes, rows)
+
+
+def wide_build(name, shape, fsizes, B):
+    """A wide-family case on the GPU in train mode, its seed set: model, oracle spec, fp32 state dict, inputs."""
     from bcnf_amd import CondRealNVP_v2
-    shape, fsizes, B = WIDE[name]
     C = shape["n_conditions"]
     torch.manual_seed(7)
     if fsizes is None:
@@ -407,11 +434,16 @@ def wide_case(name):
     y = torch.randn(B, spec.size, generator=g)
     cond = torch.randn(B, 30, 3, generator=g) if fsizes else torch.randn(B, C, generator=g)
     m.fused.set_seed(0xA11CE0000 + B)
-    case = types.SimpleNamespace(name=name, m=m, spec=spec, sd=sd, y=y, cond=cond, wide=True)
-    case.masks = _wide_records(case, OFFSET)
-    S = 2 if spec.two_way else 1
-    host = case.masks.cpu()
-    case.ref = oracle_run(case, lambda k, half, li: host[k * S + (half == "b"), li])
+    return types.SimpleNamespace(name=name, m=m, spec=spec, sd=sd, y=y, cond=cond, wide=True)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case(name):
+    """wide_build of a WIDE / WIDE_EDGE case with the fp64 training step under the restated masks of (seed, OFFSET)."""
+    shape, fsizes, B = WIDE.get(name) or WIDE_EDGE[name]
+    case = wide_build(name, shape, fsizes, B)
+    case.masks = _wide_records(case, OFFSET)          # for assert_record_masks_are_independent_draws; not the oracle's
+    case.ref = oracle_run(case, wide_keep(case, OFFSET, B))
     return case
 
 
@@ -455,3 +487,83 @@ def test_wide_training_step_vs_fp64_oracle(name, path):
     (_wide_fold taken)."""
     case = wide_case(name)
     check(case, path, compare(gpu_run(case, path), case.ref))
+
+
+@pytest.mark.parametrize("name", ["w96", "w40_two_way"])
+def test_wide_nosave_training_forward_vs_fp64_oracle(name):
+    """The training forward under no_grad (wide_forward with save = false: the chain on the two A ping-pong buffers,
+    no G, no records) at (seed, OFFSET): z and log|det J| against the oracle under the restated masks, at the eval
+    gate. It leaves no records, so only the host masks can reach it."""
+    case = wide_case(name)
+    m, st = case.m, case.m.fused
+    m.train()
+    st.rng_state()[1] = OFFSET
+    with torch.no_grad():
+        z = m(case.y.to(DEV), case.cond.to(DEV), log_det_J=True)
+        ldj = m.log_det_J
+    assert not z.requires_grad
+    assert int(st.rng_state()[1].item()) == OFFSET + 1, "the RNG offset advances once per launch"
+    rows = [(k, close(g.cpu(), case.ref[k], **VAL)[0], _ratio(g.cpu(), case.ref[k], **VAL))
+            for k, g in (("z", z), ("ldj", ldj))]
+    print(f"\nTRAIN_PARITY {name} nosave-forward: z {rows[0][2]:.3f} ldj {rows[1][2]:.3f} of the gate")
+    assert all(ok for _, ok, _ in rows), rows
+
+
+def _wide_inverse_inputs(case, B):
+    """(latents, conditions, fp64 state dict, fp64 features) of a B-row inverse of the case: the first B conditions."""
+    spec = case.spec
+    zl = torch.randn(B, spec.size, generator=torch.Generator().manual_seed(B))
+    cond = case.cond[:B]
+    sd64 = {k: v.double() for k, v in case.sd.items()}
+    h64 = O.feature_forward(sd64, spec, cond.double()) if spec.feature_sizes else cond.double()
+    return zl, cond, sd64, h64
+
+
+WIDE_TRAIN_INVERSE = [("w96", 1), ("w96", 257), ("w40_two_way", 37), ("w24_c13", 37), ("w150_nh8", 131),
+                      ("fc_large_B64", 64)]
+
+
+@pytest.mark.parametrize("name,B", WIDE_TRAIN_INVERSE, ids=[f"{n}-B{B}" for n, B in WIDE_TRAIN_INVERSE])
+def test_wide_training_mode_inverse_vs_fp64_oracle(name, B):
+    """model.train(); model.inverse(): wide_inverse with rng. It draws with the forward's tags (link: 16 v; chain
+    GEMM: 16 v + l) in the inverse's block order (two_way: real blocks in reverse, nn_a's half before nn_b's), the
+    rows being the latent rows, and saves no records: the oracle's masks are the host restatement. The gate is the
+    eval inverse's of tests/test_gpu_wide.py (`close` defaults). Control: the oracle under the masks of OFFSET + 1
+    fails the same gate, so the gate sees the masks."""
+    case = wide_case(name)
+    m, st, spec = case.m, case.m.fused, case.spec
+    zl, cond, sd64, h64 = _wide_inverse_inputs(case, B)
+    ref = O.model_inverse(sd64, spec, zl.double(), h64, training=True, keep=wide_keep(case, OFFSET, B))
+    ref_next = O.model_inverse(sd64, spec, zl.double(), h64, training=True, keep=wide_keep(case, OFFSET + 1, B))
+    m.train()
+    st.rng_state()[1] = OFFSET
+    with torch.no_grad():
+        inv = m.inverse(zl.to(DEV), cond.to(DEV)).cpu()
+    assert int(st.rng_state()[1].item()) == OFFSET + 1, "the offset advances once per inverse launch"
+    ok, err = close(inv, ref, **VAL)
+    print(f"\nTRAIN_PARITY {name}-B{B} inverse: {_ratio(inv, ref, **VAL):.3f} of the gate "
+          f"(against the masks of the next offset: {_ratio(inv, ref_next, **VAL):.1f})")
+    assert ok, err
+    assert not close(inv, ref_next, **VAL)[0]              # the next offset's masks are not this launch's
+
+
+def test_wide_training_mode_sample_vs_fp64_oracle():
+    """sample(outer=True) of a wide model left in train mode: the cond_index path of wide_inverse (features once per
+    condition, the masks by latent row), four launches (conditions 4 + 3, samples 3 + 2: 12, 8, 9 and 6 rows), each at
+    its own offset; the oracle draws the same CPU z stream by seeding."""
+    case = wide_case("w96")
+    m, st, spec = case.m, case.m.fused, case.spec
+    traj = case.cond[:7]
+    m.train()
+    st.rng_state()[1] = OFFSET
+    torch.manual_seed(123)
+    got = m.sample(5, traj, outer=True, batch_size=4, sample_batch_size=3)
+    assert int(st.rng_state()[1].item()) == OFFSET + 4, "the offset advances once per launch"
+    sd64 = {k: v.double() for k, v in case.sd.items()}
+    torch.manual_seed(123)                                 # the float32 z stream; float64 from the first coupling on
+    ref = O.sample(sd64, spec, 5, traj.double(), outer=True, batch_size=4, sample_batch_size=3,
+                   keeps=lambda n, rows: wide_keep(case, OFFSET + n, rows))
+    assert got.shape == ref.shape == (5, 7, spec.size)
+    ok, err = close(got, ref, **VAL)
+    print(f"\nTRAIN_PARITY w96 sample: {_ratio(got, ref, **VAL):.3f} of the gate")
+    assert ok, err

@@ -7,8 +7,8 @@ What tests/test_gpu_variants.py has is one even-width fixture per layer in eval 
      unfold_grad() against W[:, :n] + W[:, n:] F64 and G F64^T, F64 from torch.fft.rfft of the identity, at odd widths,
      three width groups, and a group holding two row counts;
   b. eval parity (z, ldj, log_prob, inverse, every gradient, dL/dy, dL/dh) at those shapes, B = 1 included;
-  c. training mode with the launch's own masks: the wide records for the FFT stack (the mechanism of
-     tests/test_gpu_train_parity.py), forward hooks on nn.Dropout for the layerwise AnyGLU stack;
+  c. training mode with the launch's masks: the host restatement of the wide draw for the FFT stack (the mechanism
+     of tests/test_gpu_train_parity.py), forward hooks on nn.Dropout for the layerwise AnyGLU stack;
   d. TrainStep on an FFT model: graph replay == eager bit for bit, three steps against torch.optim.Adam on the fp64
      oracle (the gradient Adam is handed, in the reference's layout), and no stale effective weights or pack afterwards;
   e. sample() values and log-densities.
@@ -32,7 +32,7 @@ from conftest import close
 from oracle import cnf_oracle as O
 from test_gpu_sample_logprob import _gate_lp, _sample_reference
 from test_gpu_train_parity import (GRAD, OFFSET, VAL, _ratio, _wide_records, assert_record_masks_are_independent_draws,
-                                   compare, gpu_run, oracle_run)
+                                   compare, gpu_run, oracle_run, wide_keep)
 
 pytestmark = pytest.mark.gpu
 
@@ -249,14 +249,13 @@ FFT_TRAIN = ["odd", "two_way", "cfg175", "feat"]
 
 @functools.lru_cache(maxsize=None)
 def fft_train_case(name):
-    """The case with the masks of one saving forward launch at (seed, OFFSET) read from its records, and the fp64
-    training step under those masks (wide_case of tests/test_gpu_train_parity.py for an FFTWideStack)."""
+    """The case with the fp64 training step under the host restatement of the masks of a launch at (seed, OFFSET)
+    (wide_case of tests/test_gpu_train_parity.py for an FFTWideStack, which runs the same kernels), and the masks of
+    one saving forward launch read from its records for the independence checks."""
     case = case_of(name)
     case.m.train()
     case.masks = _wide_records(case, OFFSET)
-    S = 2 if case.spec.two_way else 1
-    host = case.masks.cpu()
-    case.ref = oracle_run(case, lambda k, half, li: host[k * S + (half == "b"), li])
+    case.ref = oracle_run(case, wide_keep(case, OFFSET, case.y.shape[0]))
     return case
 
 
