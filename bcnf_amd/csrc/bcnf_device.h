@@ -20,6 +20,7 @@
 #define BCNF_TSTRIDE 17        // padded row stride of the [16 samples][16] LDS tiles (bank spread)
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef float floatx2 __attribute__((ext_vector_type(2)));
 
 // HIP failures travel in the status code only (BCNF_ERR_HIP_BASE + the hipError_t, include/bcnf_amd.h): the library
 // keeps no error state between calls.

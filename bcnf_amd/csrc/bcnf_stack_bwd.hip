@@ -81,7 +81,11 @@ __device__ __forceinline__ void bwd_grad_jobs(const float* __restrict__ Td, cons
 constexpr int BWD_WG = 2 * BCNF_WG;
 constexpr int BWD_G4 = 3;                // float4 per thread of the derivative slot: gd[NH], S, ya, yb (NH <= 9)
 
-template <int NH>
+// BC: a D = 19 stack, whose Q^T and T / S head sections are in broadcast form (L.qbc): the compute waves read only
+// the live words of those sections (47 LDS reads per block instead of 56), and the helpers stage only the record's live
+// quads (RecB::live_quad: 3 float4 per thread at NH = 7, where the whole record takes STAGE_REC = 4); the dead words
+// of the LDS ring keep whatever they held.
+template <int NH, bool BC>
 __global__ __launch_bounds__(BWD_WG) void k_backward(BcnfLayout L, const float* __restrict__ pk,
                                                      const float* __restrict__ dz, const float* __restrict__ dldj,
                                                      const float* __restrict__ dloss, int nll, long long B,
@@ -121,8 +125,23 @@ __global__ __launch_bounds__(BWD_WG) void k_backward(BcnfLayout L, const float* 
     // activation records [k][workgroup][AR/4][256 threads] float4 (k_forward)
     const floatx4* arl = reinterpret_cast<const floatx4*>(arec) + (long long)blockIdx.x * AR::AR4 * BCNF_WG + t8;
     const long long ars = (long long)gridDim.x * AR::AR4 * BCNF_WG;
+    // float4 of the record this thread stages: n-th live quad (n = t8 + 256 i) = live quad n % LQ of lane n / LQ; a
+    // slot past the last one copies a dead quad of lane 0 onto itself. (NH = 8: the live quads take 4 float4 per
+    // thread as well, so the record is staged whole.)
+    constexpr int LQ = RBk::live_quads(BC), LSTAGE = (16 * LQ + BCNF_WG - 1) / BCNF_WG;
+    constexpr bool MAPPED = BC && LSTAGE < STAGE_REC;
+    constexpr int BSTAGE = MAPPED ? LSTAGE : STAGE_REC;
+    int six[BSTAGE];
+    if constexpr (MAPPED) {
+      const int rb4 = L.RB >> 2;
+#pragma unroll
+      for (int i = 0; i < BSTAGE; ++i) {
+        const int n = t8 + i * BCNF_WG, lane = n / LQ, c = n - lane * LQ;
+        six[i] = n < 16 * LQ ? lane * rb4 + RBk::live_quad(true, c) : RBk::dead_quad();
+      }
+    }
     struct Prep {
-      Stage<STAGE_REC> sr;
+      Stage<BSTAGE> sr;
       floatx4 rec[AR::AR4];
       float rec1[AR::AR1 > 0 ? AR::AR1 : 1];
       float sa, ba;
@@ -130,7 +149,8 @@ __global__ __launch_bounds__(BWD_WG) void k_backward(BcnfLayout L, const float* 
     const float* ar1l = arec + ar1_off(nb, gridDim.x, AR::AR4) + (long long)blockIdx.x * AR::AR1 * BCNF_WG + t8;
     const long long ar1s = (long long)gridDim.x * AR::AR1 * BCNF_WG;
     auto prep_load = [&](Prep& P, int k) {                  // block k's inputs: HBM / L2 -> registers
-      P.sr.load_t(pbk + (long long)k * RBL, RBL, t8);
+      if constexpr (MAPPED) P.sr.load_ix(pbk + (long long)k * RBL, six);
+      else P.sr.load_t(pbk + (long long)k * RBL, RBL, t8);
 #pragma unroll
       for (int i = 0; i < AR::AR4; ++i) P.rec[i] = arl[(long long)k * ars + i * BCNF_WG];
 #pragma unroll
@@ -172,7 +192,8 @@ __global__ __launch_bounds__(BWD_WG) void k_backward(BcnfLayout L, const float* 
       floatx4* gd = gsl + (k & 1) * BWD_G4 * BCNF_WG + t8;
 #pragma unroll
       for (int i = 0; i < BWD_G4; ++i) gd[i * BCNF_WG] = floatx4{gs[4 * i], gs[4 * i + 1], gs[4 * i + 2], gs[4 * i + 3]};
-      P.sr.store_t(recB + (k & 1) * RING, t8);
+      if constexpr (MAPPED) P.sr.store_ix(recB + (k & 1) * RING, six);
+      else P.sr.store_t(recB + (k & 1) * RING, t8);
     };
     // two-deep pipeline: block k-1 is rebuilt from registers loaded one interval earlier, while block k-2's
     // loads are in flight (an HBM round trip under load is longer than one interval)
@@ -242,12 +263,17 @@ __global__ __launch_bounds__(BWD_WG) void k_backward(BcnfLayout L, const float* 
         }
       }
       float* Tt = dT + cur * J::ND * TILE + tix;
-      // the record streams in consumption order (RecB): ActNorm + Q^T + the heads now, then each stage issues the
+      // the record streams in consumption order (RecB): ActNorm + Q^T, then the heads, then each stage issues the
       // reads of a later one behind a scheduling barrier, so every wait covers a few reads, not the whole record
-      // (lgkmcnt counts at most 15 outstanding: a block-wide burst of 53 reads made the mix wait for ~40 of them)
+      // (lgkmcnt counts at most 15 outstanding: a block-wide burst of 53 reads made the mix wait for ~40 of them).
+      // BC: ActNorm + Q^T are 11 reads behind the slot's 3, so the mix waits on a counted lgkmcnt with the head
+      // reads still in flight (the rotation form's 3 + 17 + 8 reads overflow the counter: its mix waits for all).
       const float* R = recB + cur * RING + j * L.RB;
       float rb[RBk::USED];
-      ld_rec<0, RBk::HID>(rb, R);                        // ActNorm, Q^T, T / S heads
+      ld_rec<0, RBk::qt_end(BC)>(rb, R);                 // ActNorm, Q^T
+      __builtin_amdgcn_sched_barrier(0);
+      ld_rec<RBk::TT, RBk::TT + RBk::head_len(BC)>(rb, R);   // T / S heads
+      ld_rec<RBk::ST, RBk::ST + RBk::head_len(BC)>(rb, R);
       __builtin_amdgcn_sched_barrier(0);
       const float* gd = gs;
       const float S = gs[NH], ya = gs[NH + 1], yb = gs[NH + 2];
@@ -255,7 +281,7 @@ __global__ __launch_bounds__(BWD_WG) void k_backward(BcnfLayout L, const float* 
       const float xb = fmaf(an_sb, yb, an_bb);
       const float e = exp_fast(S);
       float gza, gzb;
-      if (QBC_DEV(L, QBC_MIX)) mix_bc(rb + RBk::QT, gya, gyb, gza, gzb);   // g @ Q^T (identity for the last block)
+      if constexpr (BC) mix_bc(rb + RBk::QT, gya, gyb, gza, gzb);   // g @ Q^T (identity for the last block)
       else mix(rb + RBk::QT, gya, gyb, gza, gzb);
       ld16(rb + RBk::HID, R + RBk::HID);                 // hidden layer NH
       __builtin_amdgcn_sched_barrier(0);
@@ -266,7 +292,7 @@ __global__ __launch_bounds__(BWD_WG) void k_backward(BcnfLayout L, const float* 
       Tt[NH * TILE] = dT_;
       Tt[(NH + 1) * TILE] = dSp;
       float da = 0.f, da2 = 0.f;
-      if (QBC_DEV(L, QBC_HEAD)) bc9x2(dT_, rb + RBk::TT, da, dSp, rb + RBk::ST, da2);   // (uniform)
+      if constexpr (BC) bc9x2(dT_, rb + RBk::TT, da, dSp, rb + RBk::ST, da2);
       else rot16x2(dT_, rb + RBk::TT, da, dSp, rb + RBk::ST, da2);
       da += da2;
 #pragma unroll
@@ -322,8 +348,11 @@ int launch_backward(const BcnfLayout& L, const float* pk, const float* dz, const
     constexpr int NH = decltype(nh)::value;
     if (!layout_matches<NH>(L)) return BCNF_ERR_ARG;
     const dim3 grid((unsigned)((B + 15) / 16));
-    return launch<k_backward<NH>>(grid, dim3(BWD_WG), bwd_lds_bytes(L), st, L, pk, dz, dldj, dloss, nll, B, arec, dy,
-                                  d1, slab, slab_stride_of(L), part, loss_out, rng_w, guard);
+#define BWD(BC) \
+  launch<k_backward<NH, BC>>(grid, dim3(BWD_WG), bwd_lds_bytes(L), st, L, pk, dz, dldj, dloss, nll, B, arec, dy, d1, \
+                             slab, slab_stride_of(L), part, loss_out, rng_w, guard)
+    return layout_bc(L) ? BWD(true) : BWD(false);
+#undef BWD
   });
 }
 

@@ -61,7 +61,9 @@ constexpr int FWD_HEAD = 24;           // record floats the compute waves prefet
 // all four compute waves. The rest of the record streams in two stages ahead (mlp_forward_s).
 // The projection needs no separate GEMM launch and no HBM round trip, and the compute waves' loop issues no global
 // loads (the record stores of SAVE are its only VMEM traffic).
-template <int NH, bool DROP, bool SAVE, bool RAW = false>
+// BC: a D = 19 stack, whose Linear 1 y-part and mix sections are in broadcast form (L.qbc): the compute waves read
+// only those sections' live words -- 52 LDS reads per block instead of 59 (bcnf_stack_rec.h, RecF).
+template <int NH, bool DROP, bool SAVE, bool RAW, bool BC>
 __global__ __launch_bounds__(2 * BCNF_WG) void k_forward(BcnfLayout L, const float* __restrict__ pk,
                                                     const float* __restrict__ y, ProjArgs P,
                                                     long long B, float* __restrict__ z, float* __restrict__ ldj_out,
@@ -545,10 +547,11 @@ __global__ __launch_bounds__(2 * BCNF_WG) void k_forward(BcnfLayout L, const flo
     }
     __syncthreads();
     // block k + 1's head: record floats [0, FWD_HEAD), the four projection partials, the dropout multipliers
+    constexpr int HEAD_END = RecF<NH>::head_end(BC);            // (BC: W1's last quad is dead)
     float hd[FWD_HEAD], hq4[4];
     floatx4 mk0 = {1.f, 1.f, 1.f, 1.f}, mk1 = {1.f, 1.f, 1.f, 1.f};
     auto fetch_head = [&](int sl) {
-      ld_rec<0, FWD_HEAD>(hd, rec + sl * RING + j * L.RF);
+      ld_rec<0, HEAD_END>(hd, rec + sl * RING + j * L.RF);
       const float* hq = hpb + sl * 1024 + 16 * s + j;            // [sample][neuron] partial tiles
 #pragma unroll
       for (int i = 0; i < 4; ++i) hq4[i] = hq[256 * i];
@@ -572,7 +575,7 @@ __global__ __launch_bounds__(2 * BCNF_WG) void k_forward(BcnfLayout L, const flo
       const int nxt = cur == FWD_SLOTS - 1 ? 0 : cur + 1;
       float rr[RecF<NH>::USED];
 #pragma unroll
-      for (int i = 0; i < FWD_HEAD; ++i) rr[i] = hd[i];
+      for (int i = 0; i < HEAD_END; ++i) rr[i] = hd[i];
       const float hpk = ((hq4[0] + hq4[1]) + hq4[2]) + hq4[3];
       const float msk[8] = {mk0[0], mk0[1], mk0[2], mk0[3], mk1[0], mk1[1], mk1[2], mk1[3]};
       const float xa = fmaf(rr[0], ya, rr[1]);          // ActNorm (cnf.py:349)
@@ -587,7 +590,7 @@ __global__ __launch_bounds__(2 * BCNF_WG) void k_forward(BcnfLayout L, const flo
       auto emit = [&](int q) {
         if (SAVE) st4_wt(d4 + q * BCNF_WG, floatx4{ar[4 * q], ar[4 * q + 1], ar[4 * q + 2], ar[4 * q + 3]});
       };
-      mlp_forward_s<NH, SAVE, DROP>(rr, rec + cur * RING + j * L.RF, xa, hpk, msk, T, Sp, ar, emit, QBC_DEV(L, QBC_W1));
+      mlp_forward_s<NH, SAVE, DROP, BC>(rr, rec + cur * RING + j * L.RF, xa, hpk, msk, T, Sp, ar, emit);
       const float Sv = tanh_bf(Sp);                      // cnf.py:107
       const float zb = fmaf(exp_fast(Sv), xb, T);        // cnf.py:179
       ldj += Sv;                                         // cnf.py:190
@@ -603,7 +606,7 @@ __global__ __launch_bounds__(2 * BCNF_WG) void k_forward(BcnfLayout L, const flo
       }
       fetch_head(nxt);     // slot nxt is complete since the previous barrier (after the last block: unused, no
                            // branch); the reads land while the mix runs
-      if (QBC_DEV(L, QBC_MIX)) mix_bc(rr + RecF<NH>::Q, xa, zb, ya, yb);   // y @ Q (cnf.py:335); identity after the last block
+      if constexpr (BC) mix_bc(rr + RecF<NH>::Q, xa, zb, ya, yb);   // y @ Q (cnf.py:335); identity after the last block
       else mix(rr + RecF<NH>::Q, xa, zb, ya, yb);
       cur = nxt;
       PHF(1)
@@ -671,13 +674,16 @@ int launch_forward(const BcnfLayout& L, const float* pk, const float* y, const f
     constexpr int NH = decltype(nh)::value;
     if (!layout_matches<NH>(L)) return BCNF_ERR_ARG;
     if (P.Cp % 16 != 0 || P.Cp / 16 > HP_SMAX || P.C > P.Cp) return BCNF_ERR_UNSUPPORTED;
-    // the six instantiations that exist: the pack-free forward always saves (k_forward<NH, *, false, true> is none)
-#define FWD(DR, SV, RW) \
-  launch<k_forward<NH, DR, SV, RW>>(grid, dim3(2 * BCNF_WG), lds, st, L, pk, y, P, B, z, ldj, logp, rng, arec, part, R)
+    // the six instantiations that exist per record form: the pack-free forward always saves (k_forward<NH, *, false,
+    // true, *> is none)
+#define FWD1(DR, SV, RW, BC) \
+  launch<k_forward<NH, DR, SV, RW, BC>>(grid, dim3(2 * BCNF_WG), lds, st, L, pk, y, P, B, z, ldj, logp, rng, arec, part, R)
+#define FWD(DR, SV, RW) (layout_bc(L) ? FWD1(DR, SV, RW, true) : FWD1(DR, SV, RW, false))
     if (raw) return !save ? BCNF_ERR_ARG : drop ? FWD(true, true, true) : FWD(false, true, true);
     if (save) return drop ? FWD(true, true, false) : FWD(false, true, false);
     return drop ? FWD(true, false, false) : FWD(false, false, false);
 #undef FWD
+#undef FWD1
   });
 }
 

@@ -40,6 +40,17 @@ struct Stage {
 #pragma unroll
     for (int i = 0; i < N; ++i) s4[t + i * BCNF_WG] = r[i];
   }
+  // mapped form: float4 ix[i] of the source to float4 ix[i] of the slot (a record staged without its dead quads)
+  __device__ __forceinline__ void load_ix(const float* __restrict__ g, const int* ix) {
+    const floatx4* g4 = reinterpret_cast<const floatx4*>(g);
+#pragma unroll
+    for (int i = 0; i < N; ++i) r[i] = g4[ix[i]];
+  }
+  __device__ __forceinline__ void store_ix(float* __restrict__ s, const int* ix) const {
+    floatx4* s4 = reinterpret_cast<floatx4*>(s);
+#pragma unroll
+    for (int i = 0; i < N; ++i) s4[ix[i]] = r[i];
+  }
 };
 
 // Stage rows [r0, r0 + 64) x cols [c0, c0 + KC) of a row-major (nrows x ncols, ld) matrix into regs
@@ -73,15 +84,38 @@ __device__ __forceinline__ void load_rows64(const float* __restrict__ M, long lo
 }
 
 // Compile-time mirror of the forward / backward record layouts of make_layout (checked on the host).
+// A broadcast-form section (QBC_*: bc10, mix_bc, bc9x2) keeps its rotation-form size and offset -- the record sizes
+// of the D = 19 stacks are pinned (tests/test_small_arms_cpu.py) -- and its live words are the section's first ones:
+// 10 of W1's 16, 38 of Q's 64, 9 of each head transpose's 16. The words past them are dead: k_forward and k_backward
+// (BC = all three bits, the only non-zero value make_layout gives) read none of them, k_backward stages none.
+// A section's last live words are read with a ds_read_b64 / _b32, not as part of a quad: a quad whose upper words
+// nobody uses gets registers the allocator hands to the next read at once, and that read then waits for it.
+constexpr int BC_W1 = 10, BC_Q = 38, BC_HEAD = 9;    // live floats of a broadcast section
+__host__ __device__ constexpr int quads(int n) { return (n + 3) / 4; }
 template <int NH>
 struct RecF {
   static constexpr int B1 = 4, W1 = 8, HID = 24, T = 24 + 17 * (NH - 1), S = T + 17;
   static constexpr int Q = (S + 17 + 3) & ~3, MLP_END = (S + 17 + 3) & ~3, USED = Q + 64;
+  __host__ __device__ static constexpr int head_end(bool bc) { return bc ? W1 + BC_W1 : HID; }   // of [0, HID)
+  __host__ __device__ static constexpr int live_end(bool bc) { return bc ? Q + BC_Q : USED; }
 };
 template <int NH>
 struct RecB {   // consumption order (make_layout): ActNorm, Q^T, T / S heads, hidden l = NH .. 2, W1^T
   static constexpr int AN = 0, QT = 4, TT = 68, ST = 84, HID = 100, W1T = 100 + 16 * (NH - 1);
   static constexpr int USED = W1T + 16;
+  __host__ __device__ static constexpr int qt_end(bool bc) { return bc ? QT + BC_Q : TT; }
+  __host__ __device__ static constexpr int head_len(bool bc) { return bc ? BC_HEAD : 16; }
+  // the quads of a lane's record that hold a live word, in order: live_quad(c), c < live_quads(bc)
+  __host__ __device__ static constexpr int live_quads(bool bc) {
+    return bc ? quads(qt_end(true)) + 2 * quads(BC_HEAD) + (USED - HID) / 4 : USED / 4;
+  }
+  __host__ __device__ static constexpr int live_quad(bool bc, int c) {
+    if (!bc) return c;
+    const int nq = quads(qt_end(true)), nh = quads(BC_HEAD);
+    return c < nq ? c : c < nq + nh ? TT / 4 + (c - nq) : c < nq + 2 * nh ? ST / 4 + (c - nq - nh)
+                                                                        : HID / 4 + (c - nq - 2 * nh);
+  }
+  __host__ __device__ static constexpr int dead_quad() { return quads(qt_end(true)); }   // all of it dead under BC
 };
 // Activation record a training forward saves per (block, sample, lane) for the backward, so the backward never
 // recomputes the MLP: masked activations, masked GELU derivatives, tanh(s) and the block input, 2 NH + 3 floats
@@ -110,9 +144,20 @@ struct ActRec {
 
 // Burst-load floats [lo, hi) of this lane's LDS record into registers (compile-time indices, so the
 // array lives in VGPRs): one LDS wait per block instead of one per layer.
+// The n < 4 floats at e (a multiple of 4) that end a slice: one 8-byte and / or one 4-byte read.
+template <int N>
+__device__ __forceinline__ void ld_rec_tail(float* __restrict__ rr, const float* __restrict__ R, int e) {
+  static_assert(N >= 0 && N < 4, "less than a quad");
+  if (N >= 2) {
+    const floatx2 v = *reinterpret_cast<const floatx2*>(R + e);
+    rr[e] = v.x;
+    rr[e + 1] = v.y;
+  }
+  if (N & 1) rr[e + (N & 2)] = R[e + (N & 2)];
+}
 template <int LO, int HI>
 __device__ __forceinline__ void ld_rec(float* __restrict__ rr, const float* __restrict__ R) {
-  static_assert(LO % 4 == 0 && HI % 4 == 0, "record slices are 16-B aligned");
+  static_assert(LO % 4 == 0 && HI >= LO, "record slices start 16-B aligned");
   const floatx4* R4 = reinterpret_cast<const floatx4*>(R + LO);
 #pragma unroll
   for (int i = 0; i < (HI - LO) / 4; ++i) {
@@ -122,6 +167,7 @@ __device__ __forceinline__ void ld_rec(float* __restrict__ rr, const float* __re
     rr[LO + 4 * i + 2] = v.z;
     rr[LO + 4 * i + 3] = v.w;
   }
+  ld_rec_tail<(HI - LO) % 4>(rr, R, LO + (HI - LO) / 4 * 4);
 }
 
 // Nested MLP forward on the row layout (cnf.py:98-107) from a register-resident forward record.
@@ -153,26 +199,30 @@ __device__ __forceinline__ void mlp_forward(const BcnfLayout& L, const float* __
 // burst form ld_rec<FWD_HEAD, USED> let hipcc issue 17 reads after layer 1 and wait for all of them at once, then
 // 4 and 8 more each with a wait one GELU later: five exposed LDS round trips per block under four waves' load.)
 constexpr int FWD_AHEAD = 2;
-template <int NH>
+template <int NH, bool BC>
 __host__ __device__ constexpr int rf_stage_end(int l) {   // exclusive end (floats) of what stage l reads
-  return l <= NH ? 24 + 17 * (l - 1) : (l == NH + 1 ? RecF<NH>::S + 17 : RecF<NH>::USED);
+  return l <= NH ? 24 + 17 * (l - 1) : (l == NH + 1 ? RecF<NH>::S + 17 : RecF<NH>::live_end(BC));
 }
-template <int NH>
+template <int NH, bool BC>
 __host__ __device__ constexpr int rf_stage_q(int l) {     // quads issued once stage l's reads are out
   // at most 8 new quads per stage (lgkmcnt tracks 15 outstanding: a 16-read burst at the last layer made hipcc wait
   // for its oldest reads at once); whatever the cap defers goes out with the next stage, all of it by the mix
   int q = 6;
   for (int i = 1; i <= l; ++i) {
-    const int want = (rf_stage_end<NH>(i + FWD_AHEAD < NH + 2 ? i + FWD_AHEAD : NH + 2) + 3) / 4;
+    const int want = (rf_stage_end<NH, BC>(i + FWD_AHEAD < NH + 2 ? i + FWD_AHEAD : NH + 2) + 3) / 4;
     q = i >= NH + 2 ? want : (want < q + 8 ? want : q + 8);
   }
   return q;
 }
-template <int NH>
+template <int NH, bool BC>
 __device__ __forceinline__ void rf_issue(float* __restrict__ rr, const float* __restrict__ R, int l) {
   const floatx4* R4 = reinterpret_cast<const floatx4*>(R);
 #pragma unroll
-  for (int q = rf_stage_q<NH>(l - 1); q < rf_stage_q<NH>(l); ++q) {
+  for (int q = rf_stage_q<NH, BC>(l - 1); q < rf_stage_q<NH, BC>(l); ++q) {
+    if (4 * q + 4 > RecF<NH>::live_end(BC)) {           // (BC: the mix section's last two live words)
+      ld_rec_tail<RecF<NH>::live_end(BC) % 4>(rr, R, 4 * q);
+      continue;
+    }
     const floatx4 v = R4[q];
     rr[4 * q] = v.x;
     rr[4 * q + 1] = v.y;
@@ -182,19 +232,20 @@ __device__ __forceinline__ void rf_issue(float* __restrict__ rr, const float* __
   __builtin_amdgcn_sched_barrier(0);
 }
 // KEEP: the activation record goes to ar (ActRec order), and emit(q) is called right after float4 q is complete.
-template <int NH, bool KEEP, bool DROP, typename Emit>
+// BC: the broadcast form (Linear 1 here), whose dead words no stage reads (rf_stage_end, RecF::head_end).
+template <int NH, bool KEEP, bool DROP, bool BC, typename Emit>
 __device__ __forceinline__ void mlp_forward_s(float* __restrict__ rr, const float* __restrict__ R, float x, float hp,
                                               const float* __restrict__ msk, float& T, float& Sp, float* ar,
-                                              Emit&& emit, bool qbc) {
+                                              Emit&& emit) {
   static_assert(RecF<NH>::HID == 24, "stage 1 reads only the prefetched head (FWD_HEAD = 24)");
   using F = RecF<NH>;
   using AR = ActRec<NH>;
   float a = x;
 #pragma unroll
   for (int l = 1; l <= NH; ++l) {
-    rf_issue<NH>(rr, R, l);
+    rf_issue<NH, BC>(rr, R, l);
     const float* w = (l == 1) ? rr + F::W1 : rr + F::HID + 17 * (l - 2);
-    const float pre = (l == 1 && qbc) ? bc10(a, w, hp) : rot16(a, w, (l == 1) ? hp : w[16]);   // (uniform)
+    const float pre = (l == 1 && BC) ? bc10(a, w, hp) : rot16(a, w, (l == 1) ? hp : w[16]);
     if (KEEP) {
       float g, dg;
       gelu_fg(pre, g, dg);
@@ -214,11 +265,11 @@ __device__ __forceinline__ void mlp_forward_s(float* __restrict__ rr, const floa
       a = gelu_f(pre);
     }
   }
-  rf_issue<NH>(rr, R, NH + 1);
+  rf_issue<NH, BC>(rr, R, NH + 1);
   T = rr[F::T + 16];
   Sp = rr[F::S + 16];
   rot16x2(a, rr + F::T, T, a, rr + F::S, Sp);
-  rf_issue<NH>(rr, R, NH + 2);   // (empty: the mix's quads went out with stage NH)
+  rf_issue<NH, BC>(rr, R, NH + 2);   // (empty: the mix's quads went out with stage NH)
 }
 
 // Row-layout orthonormal mix: (na, nb) = (a, b) @ M with the four pre-rotated quadrants at rq
@@ -286,8 +337,10 @@ bool layout_matches(const BcnfLayout& L) {
          L.rf_s == RecF<NH>::S && L.rf_q == RecF<NH>::Q && L.RF == inv_m_rf<NH>() &&
          L.PMB == (NH + 6) * 256 + (NH - 1) * 16 + 96 && L.rb_w1t == RecB<NH>::W1T &&
          L.rb_hid == RecB<NH>::HID && L.rb_tt == RecB<NH>::TT && L.rb_st == RecB<NH>::ST && L.rb_qt == RecB<NH>::QT &&
-         L.rb_an == RecB<NH>::AN && L.RB >= RecB<NH>::USED;
+         L.rb_an == RecB<NH>::AN && L.RB >= RecB<NH>::USED && (L.qbc == 0 || L.qbc == (QBC_W1 | QBC_MIX | QBC_HEAD));
 }
+// The record form k_forward and k_backward are instantiated for (BC): every section in broadcast form, or none.
+inline bool layout_bc(const BcnfLayout& L) { return L.qbc == (QBC_W1 | QBC_MIX | QBC_HEAD); }
 
 }  // namespace bcnf_small
 #pragma GCC visibility pop
